@@ -6,6 +6,13 @@ batch 256/GPU, synthetic 224x224x3 data, random-init weights
 Single GPU:   python bench.py --steps 20 --warmup 5
 Multi-GPU:    torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
               (one process per GPU over RCCL; rank/env from torchrun)
+
+A plain run sets up, warms up, times --steps training steps and prints one
+JSON result line. --dump-outputs DIR additionally writes what the last timed
+step computed, starting from the post-initialization state (see _Rewind
+and _dump_outputs). --full is where any measurement beyond
+the headline figure belongs; the benchmark has none today, so it changes
+nothing yet.
 """
 import argparse
 import json
@@ -36,6 +43,11 @@ def main():
     ap.add_argument('--model', default='resnet50',
                     choices=['resnet50', 'inception3', 'ptb_lstm'])
     ap.add_argument('--seq-len', type=int, default=35)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='rewind the variables before the last timed step '
+                         'and write what it computed as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary measurement (none today)')
     args = ap.parse_args()
     if args.batch == 0:
         args.batch = {'resnet50': 256, 'inception3': 128,
@@ -53,28 +65,26 @@ def main():
         comm = dist.init(world, rank)
 
     loss_t, train_op = _build(args, world)
+    rewind = _Rewind() if args.dump_outputs else None
 
     sess = tf.Session()
     sess.run(tf.global_variables_initializer())
     if comm is not None:
         comm.broadcast_variables(sess)
+    if rewind is not None:
+        rewind.save(sess)
 
     # warmup
-    for _ in range(args.warmup):
-        sess.run(train_op)
-    _sync(sess, loss_t)
-    if comm is not None:
-        comm.barrier()
+    _run_steps(sess, train_op, loss_t, comm, args.warmup)
 
-    t0 = time.time()
-    for _ in range(args.steps):
-        sess.run(train_op)
-    _sync(sess, loss_t)
-    if comm is not None:
-        comm.barrier()
-    t1 = time.time()
+    if rewind is None:
+        elapsed = _run_steps(sess, train_op, loss_t, comm, args.steps)
+    else:
+        # The clock stops while the state is rewound before the last step.
+        elapsed = _run_steps(sess, train_op, loss_t, comm, args.steps - 1)
+        rewind.restore(sess)
+        elapsed += _run_steps(sess, train_op, loss_t, comm, 1)
 
-    elapsed = t1 - t0
     if comm is not None:
         elapsed = comm.max_scalar(elapsed)
 
@@ -111,7 +121,88 @@ def main():
                 'parallelism': 'dp%d' % world,
             },
         }
+        if args.dump_outputs:
+            _dump_outputs(sess, loss_t, args.dump_outputs)
         print(json.dumps(out))
+
+
+def _run_steps(sess, train_op, loss_t, comm, n):
+    """Runs n training steps to completion; returns the seconds they took."""
+    t0 = time.time()
+    for _ in range(n):
+        sess.run(train_op)
+    _sync(sess, loss_t)
+    if comm is not None:
+        comm.barrier()
+    return time.time() - t0
+
+
+class _Rewind(object):
+    """Puts every variable (weights and optimizer slots) back to its value
+    right after initialization.
+
+    Steps are not bit-reproducible (split-K partial sums are accumulated
+    with f32 atomics), and training from random init at the benchmark's
+    learning rate amplifies that rounding noise: after a few dozen steps two
+    runs of the same build no longer agree in any digit. One step from a
+    fixed state stays within rounding noise, so --dump-outputs rewinds
+    before the last timed step and two builds can be compared on what that
+    step computes."""
+
+    def __init__(self):
+        import simple_tensorflow_amd as tf
+        self._vars = tf.global_variables()
+        self._feeds = [tf.placeholder(v.value().dtype, v.value()._shape)
+                       for v in self._vars]
+        self._op = tf.group(*[v.assign(p)
+                              for v, p in zip(self._vars, self._feeds)])
+        self._saved = None
+
+    def save(self, sess):
+        self._saved = sess.run([v.value() for v in self._vars])
+
+    def restore(self, sess):
+        sess.run(self._op, feed_dict=dict(zip(self._feeds, self._saved)))
+        sess.sync()
+
+
+# Elements written per variable by --dump-outputs; larger ones are sampled.
+_DUMP_MAX_ELEMS = 1 << 16
+# Upper bound on variables.npy, well inside the 64 MB a dump may take.
+_DUMP_BUDGET_BYTES = 48 << 20
+
+
+def _dump_outputs(sess, loss_t, out_dir):
+    """Writes what a caller of the last timed train step is left with, as
+    float32 .npy files:
+
+    variables.npy  every trainable variable as that step updated it, in
+                   graph order, each flattened; a variable with more than
+                   _DUMP_MAX_ELEMS elements contributes a fixed, seeded
+                   sample of them (same indices in every run).
+    loss.npy       the loss the model gives with those variables.
+
+    The variables are fetched, not recomputed. Graph construction, the
+    initializer seeds, the synthetic batches and the state the last step
+    starts from (see _Rewind) are fixed, so runs with the same arguments
+    start from identical inputs."""
+    import numpy as np
+    import simple_tensorflow_amd as tf
+
+    os.makedirs(out_dir, exist_ok=True)
+    tvars = tf.trainable_variables()
+    values = sess.run([v.value() for v in tvars])
+    cap = min(_DUMP_MAX_ELEMS, _DUMP_BUDGET_BYTES // (4 * max(len(tvars), 1)))
+    rng = np.random.RandomState(20240229)
+    parts = []
+    for val in values:
+        flat = np.asarray(val, dtype=np.float32).reshape(-1)
+        if flat.size > cap:
+            flat = flat[np.sort(rng.randint(0, flat.size, cap))]
+        parts.append(flat)
+    np.save(os.path.join(out_dir, 'variables.npy'), np.concatenate(parts))
+    loss = np.asarray(sess.run(loss_t), dtype=np.float32)
+    np.save(os.path.join(out_dir, 'loss.npy'), loss)
 
 
 def _build(args, world):

@@ -12,6 +12,7 @@
 // no per-step H2D table upload is needed: tensor addresses change every
 // step under BFC reuse.
 #include "hip_common.h"
+#include "stf_kernels.h"
 
 #define STF_COMM_MAX_SEG 120
 

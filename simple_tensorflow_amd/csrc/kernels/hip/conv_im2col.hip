@@ -3,6 +3,7 @@
 // col[(n*P+p)*Q+q][(r*S+s)*C+c] — C-contiguous so warp lanes write
 // consecutive bytes; reads from x are C-contiguous too.
 #include "hip_common.h"
+#include "stf_kernels.h"
 
 namespace {
 
@@ -125,26 +126,31 @@ __global__ void Col2ImKernelV8(const __bf16* __restrict__ dcol,
 
 }  // namespace
 
-extern "C" hipError_t stf_im2col_bf16(const void* x, void* col, int N, int H,
-                                      int W, int C, int R, int S, int sh,
-                                      int sw, int ph, int pw, int P, int Q,
-                                      int64_t ld, hipStream_t stream) {
-  ConvGeom g{N, H, W, C, R, S, 0, sh, sw, ph, pw, P, Q};
-  int vec = (C % 8 == 0) ? 8 : 1;
-  int64_t total = (int64_t)N * P * Q * R * S * (C / vec);
+namespace {
+ConvGeom DeviceGeom(const StfConvGeom& g) {
+  return ConvGeom{g.n, g.h, g.w, g.c, g.r, g.s, 0, g.sh, g.sw, g.ph, g.pw,
+                  g.p, g.q};
+}
+}  // namespace
+
+extern "C" hipError_t stf_im2col_bf16(const void* x, void* col,
+                                      const StfConvGeom* sg, int64_t ld,
+                                      hipStream_t stream) {
+  ConvGeom g = DeviceGeom(*sg);
+  int vec = (g.C % 8 == 0) ? 8 : 1;
+  int64_t total = (int64_t)g.N * g.P * g.Q * g.R * g.S * (g.C / vec);
   hipLaunchKernelGGL(Im2ColKernel, ElemwiseGrid(total, 256, 1), dim3(256), 0,
                      stream, (const __bf16*)x, (__bf16*)col, g, total, vec,
                      ld);
   return hipGetLastError();
 }
 
-extern "C" hipError_t stf_col2im_bf16(const void* dcol, void* dx, int N, int H,
-                                      int W, int C, int R, int S, int sh,
-                                      int sw, int ph, int pw, int P, int Q,
+extern "C" hipError_t stf_col2im_bf16(const void* dcol, void* dx,
+                                      const StfConvGeom* sg,
                                       hipStream_t stream) {
-  ConvGeom g{N, H, W, C, R, S, 0, sh, sw, ph, pw, P, Q};
-  int64_t total = (int64_t)N * H * W * C;
-  if (C % 8 == 0) {
+  ConvGeom g = DeviceGeom(*sg);
+  int64_t total = (int64_t)g.N * g.H * g.W * g.C;
+  if (g.C % 8 == 0) {
     int64_t total8 = total / 8;
     hipLaunchKernelGGL(Col2ImKernelV8, ElemwiseGrid(total8, 256, 1),
                        dim3(256), 0, stream, (const __bf16*)dcol,

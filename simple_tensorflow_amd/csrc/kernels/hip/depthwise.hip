@@ -3,6 +3,7 @@
 // channel-vectorized where C%8==0 is not required (grid-stride, 16B loads
 // opportunistic via contiguous channel runs).
 #include "hip_common.h"
+#include "stf_kernels.h"
 
 namespace {
 

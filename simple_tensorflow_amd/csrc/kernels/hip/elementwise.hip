@@ -4,6 +4,7 @@
 // reference's ~70 Eigen-GPU cwise kernels (cwise_op_gpu_*.cu.cc) with one
 // templated family.
 #include "hip_common.h"
+#include "stf_kernels.h"
 
 namespace {
 
@@ -161,18 +162,6 @@ __global__ void CastKernel<float, int32_t>(const float* __restrict__ x,
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     y[i] = (int32_t)x[i];
-}
-
-// ---- AddN ----
-template <typename T>
-__global__ void AddNKernel(const T* const* __restrict__ ptrs, int num,
-                           T* __restrict__ y, int64_t n) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float acc = 0.f;
-    for (int k = 0; k < num; ++k) acc += (float)ptrs[k][i];
-    y[i] = (T)acc;
-  }
 }
 
 // ---- scale by immediate ----
@@ -422,19 +411,6 @@ extern "C" hipError_t stf_cast(int sdt, int ddt, const void* x, void* y,
   CASTCASE(4, 5, int64_t, bool)
 #undef CASTCASE
   return hipErrorInvalidValue;
-}
-
-extern "C" hipError_t stf_addn(int dtype, const void* const* dev_ptr_array,
-                               int num, void* y, int64_t n,
-                               hipStream_t stream) {
-  dim3 grid = ElemwiseGrid(n, 256, 4);
-  if (dtype == 0)
-    hipLaunchKernelGGL((AddNKernel<float>), grid, dim3(256), 0, stream,
-                       (const float* const*)dev_ptr_array, num, (float*)y, n);
-  else
-    hipLaunchKernelGGL((AddNKernel<__bf16>), grid, dim3(256), 0, stream,
-                       (const __bf16* const*)dev_ptr_array, num, (__bf16*)y, n);
-  return hipGetLastError();
 }
 
 extern "C" hipError_t stf_scale(int dtype, const void* x, void* y, int64_t n,

@@ -10,6 +10,10 @@
 // Interior blocks take the glds fast path; edge blocks (M/N remainder or K
 // tail) stage through a guarded scalar path into the same swizzled image.
 #include "hip_common.h"
+#include "stf_kernels.h"
+
+#include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -344,121 +348,113 @@ __launch_bounds__(256) __global__ void GemmBf16NT(
   }
 }
 
-template <bool A_KM, bool B_KM, bool OUT_BF16, bool FUSE_RELU>
-hipError_t LaunchVariant(const uint16_t* A, const uint16_t* B, void* C,
-                         const float* bias, int64_t M, int64_t N, int64_t K,
-                         int64_t lda, int64_t ldb, float beta,
-                         hipStream_t stream) {
-  static const bool no_sb = getenv("STF_GEMM_NO_SB") != nullptr;
-  bool short_k = !no_sb && K <= 4 * 64;
-  LinearAG a_ag{A, lda};
-  auto launch = [&](auto kern, int BM, int BN) {
-    int64_t blocks = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, stream,
-                       a_ag, B, C, bias, M, N, K, ldb, beta, 1);
-  };
-#define STF_PICK(WM_, WN_, TM, TN)                                           do {                                                                         if (short_k)                                                                 launch(GemmBf16NT<2, 2, WM_, WN_, A_KM, B_KM, OUT_BF16, FUSE_RELU,                           false, false>,                                                  TM, TN);                                                          else                                                                         launch(GemmBf16NT<2, 2, WM_, WN_, A_KM, B_KM, OUT_BF16, FUSE_RELU>,               TM, TN);                                                        } while (0)
-  if (M <= 32 && N >= 128) {
+// ---------------------------------------------------------------------------
+// Host side. Every caller wants bias = nullptr, beta = 0, no ReLU, and bf16
+// output (plain GEMM, conv forward) or f32 split-K accumulation, so only
+// those instantiations exist. OUT_BF16/FUSE_RELU and the bias/beta kernel
+// arguments are therefore constant per launch path; folding them out of the
+// kernel template would change tuned device code and needs GPU timing, so
+// the kernel keeps them.
+// ---------------------------------------------------------------------------
+template <int WAVES_M_, int WAVES_N_, int WM_, int WN_>
+struct Tile {
+  static constexpr int WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;
+  static constexpr int WM = WM_, WN = WN_;
+  static constexpr int BM = WAVES_M * WM * 16, BN = WAVES_N * WN * 16;
+};
+
+// The one tile choice for GemmBf16NT: calls f(Tile<...>{}) for an [M, N]
+// output. SKINNY enables the 32x128 tile (plain and split-K GEMM only).
+template <bool SKINNY, class F>
+void PickTile(int64_t M, int64_t N, F f) {
+  if (SKINNY && M <= 32 && N >= 128) {
     // Skinny-M (RNN batch rows, FC with tiny batch): a 32-row tile spans the
     // whole M in one block row, so B is streamed exactly once; 1x4 wave
     // layout keeps all four waves on distinct N columns.
-    if (short_k)
-      launch(GemmBf16NT<1, 4, 2, 2, A_KM, B_KM, OUT_BF16, FUSE_RELU, false,
-                        false>, 32, 128);
-    else
-      launch(GemmBf16NT<1, 4, 2, 2, A_KM, B_KM, OUT_BF16, FUSE_RELU>, 32,
-             128);
+    if constexpr (SKINNY) f(Tile<1, 4, 2, 2>{});
   } else if (N >= 128 && M >= 128) {
-    STF_PICK(4, 4, 128, 128);
+    f(Tile<2, 2, 4, 4>{});
   } else if (N >= 128) {
-    STF_PICK(2, 4, 64, 128);
+    f(Tile<2, 2, 2, 4>{});
   } else if (M >= 128) {
-    STF_PICK(4, 2, 128, 64);
+    f(Tile<2, 2, 4, 2>{});
   } else {
-    STF_PICK(2, 2, 64, 64);
+    f(Tile<2, 2, 2, 2>{});
   }
-#undef STF_PICK
+}
+
+// Which host entry is launching; fixes the kernel variants it may use.
+enum class Path { kPlain, kSplitK, kConvFwd, kConvDw };
+
+// Launches GemmBf16NT on the picked tile. Split-K paths accumulate f32
+// atomics, the others write bf16. The skinny-M tile applies to the linear
+// GEMMs only; single_buf (DBUF=false, short K loops) to the plain GEMM only.
+template <Path P, bool A_KM, bool B_KM, class AAG>
+hipError_t LaunchNT(const AAG& a_ag, const void* B, void* C, int64_t M,
+                    int64_t N, int64_t K, int64_t ldb, int splitk,
+                    bool single_buf, hipStream_t stream) {
+  constexpr bool SPLITK = P == Path::kSplitK || P == Path::kConvDw;
+  constexpr bool SKINNY = P == Path::kPlain || P == Path::kSplitK;
+  PickTile<SKINNY>(M, N, [&](auto t) {
+    using T = decltype(t);
+    int64_t blocks =
+        ((M + T::BM - 1) / T::BM) * ((N + T::BN - 1) / T::BN) * splitk;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, stream,
+                         a_ag, (const uint16_t*)B, C, (const float*)nullptr,
+                         M, N, K, ldb, 0.f, splitk);
+    };
+    if constexpr (P == Path::kPlain) {
+      if (single_buf)
+        return launch(GemmBf16NT<T::WAVES_M, T::WAVES_N, T::WM, T::WN, A_KM,
+                                 B_KM, !SPLITK, false, SPLITK, false, AAG>);
+    }
+    launch(GemmBf16NT<T::WAVES_M, T::WAVES_N, T::WM, T::WN, A_KM, B_KM,
+                      !SPLITK, false, SPLITK, true, AAG>);
+  });
   return hipGetLastError();
 }
 
-template <bool A_KM, bool B_KM>
-hipError_t LaunchSplitK(const uint16_t* A, const uint16_t* B, float* C,
-                        int64_t M, int64_t N, int64_t K, int64_t lda,
-                        int64_t ldb, int splitk, hipStream_t stream) {
-  LinearAG a_ag{A, lda};
-  auto launch = [&](auto kern, int BM, int BN) {
-    int64_t blocks = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * splitk;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, stream,
-                       a_ag, B, C, nullptr, M, N, K, ldb, 0.f, splitk);
-  };
-  if (M <= 32 && N >= 128) {
-    launch(GemmBf16NT<1, 4, 2, 2, A_KM, B_KM, false, false, true>, 32, 128);
-  } else if (N >= 128 && M >= 128) {
-    launch(GemmBf16NT<2, 2, 4, 4, A_KM, B_KM, false, false, true>, 128, 128);
-  } else if (N >= 128) {
-    launch(GemmBf16NT<2, 2, 2, 4, A_KM, B_KM, false, false, true>, 64, 128);
-  } else if (M >= 128) {
-    launch(GemmBf16NT<2, 2, 4, 2, A_KM, B_KM, false, false, true>, 128, 64);
-  } else {
-    launch(GemmBf16NT<2, 2, 2, 2, A_KM, B_KM, false, false, true>, 64, 64);
-  }
-  return hipGetLastError();
+// Runtime (a_km, b_km) -> compile-time staging layout.
+template <class F>
+hipError_t WithLayout(int a_km, int b_km, F f) {
+  std::true_type km;
+  std::false_type nt;
+  if (a_km && b_km) return f(km, km);
+  if (a_km) return f(km, nt);
+  if (b_km) return f(nt, km);
+  return f(nt, nt);
 }
 
 }  // namespace
-
-extern "C" int stf_gemm_bf16_8ph_ok(int64_t M, int64_t N, int64_t K);
-extern "C" hipError_t stf_gemm_bf16_8ph(const void* A, const void* B, void* C,
-                                        const void* bias_f32, int64_t M,
-                                        int64_t N, int64_t K, int64_t lda,
-                                        int64_t ldb, int out_bf16,
-                                        int fuse_relu, hipStream_t stream);
 
 // General entry. a_km/b_km select the contraction-major (transposed-staging)
 // path per operand; lda/ldb are row strides of the stored layouts
 // (a_km ? [K,M] : [M,K], b_km ? [K,N] : [N,K]).
 extern "C" hipError_t stf_gemm_bf16(const void* A, const void* B, void* C,
-                                    const void* bias_f32, int64_t M, int64_t N,
-                                    int64_t K, int64_t lda, int64_t ldb,
-                                    float beta, int a_km, int b_km,
-                                    int out_bf16, int fuse_relu,
-                                    hipStream_t stream) {
+                                    int64_t M, int64_t N, int64_t K,
+                                    int64_t lda, int64_t ldb, int a_km,
+                                    int b_km, hipStream_t stream) {
   // Fat NT tiles take the 256² 8-phase template (guide §5 top rung);
   // STF_NO_8PH reverts to the 128² step-3 kernel for A/B comparison.
   static const bool no_8ph = getenv("STF_NO_8PH") != nullptr;
-  if (!no_8ph && !a_km && !b_km && beta == 0.f &&
-      stf_gemm_bf16_8ph_ok(M, N, K))
-    return stf_gemm_bf16_8ph(A, B, C, bias_f32, M, N, K, lda, ldb, out_bf16,
-                             fuse_relu, stream);
-  const uint16_t* a = (const uint16_t*)A;
-  const uint16_t* b = (const uint16_t*)B;
-  const float* bias = (const float*)bias_f32;
-  int sel = (a_km ? 8 : 0) | (b_km ? 4 : 0) | (out_bf16 ? 2 : 0) |
-            (fuse_relu ? 1 : 0);
-  switch (sel) {
-#define STF_CASE(AK, BK_, OB, FR)                                         \
-  case ((AK ? 8 : 0) | (BK_ ? 4 : 0) | (OB ? 2 : 0) | (FR ? 1 : 0)):      \
-    return LaunchVariant<AK, BK_, OB, FR>(a, b, C, bias, M, N, K, lda,    \
-                                          ldb, beta, stream)
-    STF_CASE(false, false, false, false);
-    STF_CASE(false, false, false, true);
-    STF_CASE(false, false, true, false);
-    STF_CASE(false, false, true, true);
-    STF_CASE(false, true, false, false);
-    STF_CASE(false, true, false, true);
-    STF_CASE(false, true, true, false);
-    STF_CASE(false, true, true, true);
-    STF_CASE(true, false, false, false);
-    STF_CASE(true, false, false, true);
-    STF_CASE(true, false, true, false);
-    STF_CASE(true, false, true, true);
-    STF_CASE(true, true, false, false);
-    STF_CASE(true, true, false, true);
-    STF_CASE(true, true, true, false);
-    STF_CASE(true, true, true, true);
-#undef STF_CASE
-  }
-  return hipErrorInvalidValue;
+  if (!no_8ph && !a_km && !b_km && stf_gemm_bf16_8ph_ok(M, N, K))
+    return stf_gemm_bf16_8ph_side(A, B, C, nullptr, M, N, K, lda, ldb, stream);
+  static const bool no_sb = getenv("STF_GEMM_NO_SB") != nullptr;
+  bool short_k = !no_sb && K <= 4 * 64;
+  LinearAG a_ag{(const uint16_t*)A, lda};
+  return WithLayout(a_km, b_km, [&](auto akm, auto bkm) {
+    return LaunchNT<Path::kPlain, decltype(akm)::value,
+                    decltype(bkm)::value>(a_ag, B, C, M, N, K, ldb, 1,
+                                          short_k, stream);
+  });
+}
+
+// C[M,N] = A[M,K] * B[N,K]^T, both operands contraction-innermost.
+extern "C" hipError_t stf_gemm_bf16_nt(const void* A, const void* B, void* C,
+                                       int64_t M, int64_t N, int64_t K,
+                                       hipStream_t stream) {
+  return stf_gemm_bf16(A, B, C, M, N, K, K, K, 0, 0, stream);
 }
 
 // Split-K for skinny-output huge-K GEMMs (dW): partial products atomically
@@ -469,128 +465,42 @@ extern "C" hipError_t stf_gemm_bf16_splitk(const void* A, const void* B,
                                            int64_t K, int64_t lda, int64_t ldb,
                                            int a_km, int b_km, int splitk,
                                            hipStream_t stream) {
-  const uint16_t* a = (const uint16_t*)A;
-  const uint16_t* b = (const uint16_t*)B;
-  float* c = (float*)C_f32;
-  if (a_km && b_km)
-    return LaunchSplitK<true, true>(a, b, c, M, N, K, lda, ldb, splitk,
-                                    stream);
-  if (a_km)
-    return LaunchSplitK<true, false>(a, b, c, M, N, K, lda, ldb, splitk,
-                                     stream);
-  if (b_km)
-    return LaunchSplitK<false, true>(a, b, c, M, N, K, lda, ldb, splitk,
-                                     stream);
-  return LaunchSplitK<false, false>(a, b, c, M, N, K, lda, ldb, splitk,
-                                    stream);
-}
-
-// Legacy NT entries (both operands row-major with contraction innermost).
-extern "C" hipError_t stf_gemm_bf16_nt_splitk(const void* A, const void* B,
-                                              void* C_f32, int64_t M,
-                                              int64_t N, int64_t K, int splitk,
-                                              hipStream_t stream) {
-  return stf_gemm_bf16_splitk(A, B, C_f32, M, N, K, K, K, 0, 0, splitk,
-                              stream);
-}
-
-// C[M,N] = A[M,K] * B[N,K]^T (+ beta*C) (+bias) (+relu)
-extern "C" hipError_t stf_gemm_bf16_nt(const void* A, const void* B, void* C,
-                                       const void* bias_f32, int64_t M,
-                                       int64_t N, int64_t K, float beta,
-                                       int out_bf16, int fuse_relu,
-                                       hipStream_t stream) {
-  return stf_gemm_bf16(A, B, C, bias_f32, M, N, K, K, K, beta, 0, 0,
-                       out_bf16, fuse_relu, stream);
+  LinearAG a_ag{(const uint16_t*)A, lda};
+  return WithLayout(a_km, b_km, [&](auto akm, auto bkm) {
+    return LaunchNT<Path::kSplitK, decltype(akm)::value,
+                    decltype(bkm)::value>(a_ag, B, C_f32, M, N, K, ldb,
+                                          splitk, false, stream);
+  });
 }
 
 // Implicit-GEMM Conv2D backprop-filter: dW[rsc, Cout] = im2col(x)^T * dy,
 // contraction over the NPQ output pixels, split-K with f32 atomics. The
-// column matrix is generated inside the K-major A staging (ConvAG) — the
-// materialized im2col buffer and its cache disappear (reference analog:
-// conv_grad_filter_ops.cc ThenConvolveBackwardFilterWithAlgorithm).
-extern "C" hipError_t stf_conv2d_dw_splitk(
-    const void* x, const void* dy, void* dw_f32, const void* zero16, int n,
-    int h, int w, int c, int r, int s_, int sh, int sw, int ph, int pw,
-    int p, int q, int64_t cout, int splitk, hipStream_t stream) {
-  if ((c % 8) != 0) return hipErrorInvalidValue;
-  ConvAG ag;
-  ag.x = (const uint16_t*)x;
-  ag.zero16 = (const uint16_t*)zero16;
-  ag.div_pq.init((uint32_t)(p * q));
-  ag.div_q.init((uint32_t)q);
-  ag.div_c.init((uint32_t)c);
-  ag.div_s.init((uint32_t)s_);
-  ag.H = h; ag.W = w; ag.C = c; ag.S = s_;
-  ag.sh = sh; ag.sw = sw; ag.ph = ph; ag.pw = pw;
-  ag.rsc = (int64_t)r * s_ * c;
-  int64_t M = ag.rsc;            // dW rows
-  int64_t N = cout;
-  int64_t K = (int64_t)n * p * q;  // contraction: output pixels
-  const uint16_t* b = (const uint16_t*)dy;
-  float* cptr = (float*)dw_f32;
-  auto launch = [&](auto kern, int BM, int BN) {
-    int64_t blocks = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * splitk;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, stream,
-                       ag, b, cptr, nullptr, M, N, K, cout, 0.f, splitk);
-  };
-  if (N >= 128 && M >= 128) {
-    launch(GemmBf16NT<2, 2, 4, 4, true, true, false, false, true, true,
-                      ConvAG>, 128, 128);
-  } else if (N >= 128) {
-    launch(GemmBf16NT<2, 2, 2, 4, true, true, false, false, true, true,
-                      ConvAG>, 64, 128);
-  } else if (M >= 128) {
-    launch(GemmBf16NT<2, 2, 4, 2, true, true, false, false, true, true,
-                      ConvAG>, 128, 64);
-  } else {
-    launch(GemmBf16NT<2, 2, 2, 2, true, true, false, false, true, true,
-                      ConvAG>, 64, 64);
-  }
-  return hipGetLastError();
+// column matrix is generated inside the K-major A staging (ConvAG) — no
+// materialized im2col buffer (reference analog: conv_grad_filter_ops.cc
+// ThenConvolveBackwardFilterWithAlgorithm).
+extern "C" hipError_t stf_conv2d_dw_splitk(const void* x, const void* dy,
+                                           void* dw_f32, const void* zero16,
+                                           const StfConvGeom* g, int splitk,
+                                           hipStream_t stream) {
+  if ((g->c % 8) != 0) return hipErrorInvalidValue;
+  ConvAG ag = MakeConvAG(*g, x, zero16);
+  int64_t K = (int64_t)g->n * g->p * g->q;  // contraction: output pixels
+  return LaunchNT<Path::kConvDw, true, true>(
+      ag, dy, dw_f32, ag.rsc, g->cout, K, g->cout, splitk, false, stream);
 }
+
 // Implicit-GEMM Conv2D forward through the general NT template: the column
 // matrix row (one output pixel's [r,s,c] window) is generated inside the A
 // staging by ConvAG — covers the shapes the 256-row 8-phase kernel cannot
 // take (couts or M not multiples of its tile). Weights stay [rsc, K]
 // contraction-major (B_KM staging transposes in-register).
-extern "C" hipError_t stf_conv2d_fwd_nt(
-    const void* x, const void* w, void* y, const void* zero16, int n, int h,
-    int w_, int c, int r, int s_, int sh, int sw, int ph, int pw, int p,
-    int q, int64_t cout, int64_t rscp, hipStream_t stream) {
-  if ((c % 8) != 0) return hipErrorInvalidValue;
-  ConvAG ag;
-  ag.x = (const uint16_t*)x;
-  ag.zero16 = (const uint16_t*)zero16;
-  ag.div_pq.init((uint32_t)(p * q));
-  ag.div_q.init((uint32_t)q);
-  ag.div_c.init((uint32_t)c);
-  ag.div_s.init((uint32_t)s_);
-  ag.H = h; ag.W = w_; ag.C = c; ag.S = s_;
-  ag.sh = sh; ag.sw = sw; ag.ph = ph; ag.pw = pw;
-  ag.rsc = (int64_t)r * s_ * c;
-  int64_t M = (int64_t)n * p * q;
-  int64_t N = cout;
-  int64_t K = rscp;
-  const uint16_t* b = (const uint16_t*)w;
-  auto launch = [&](auto kern, int BM, int BN) {
-    int64_t blocks = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, stream,
-                       ag, b, y, nullptr, M, N, K, cout, 0.f, 1);
-  };
-  if (N >= 128 && M >= 128) {
-    launch(GemmBf16NT<2, 2, 4, 4, false, true, true, false, false, true,
-                      ConvAG>, 128, 128);
-  } else if (N >= 128) {
-    launch(GemmBf16NT<2, 2, 2, 4, false, true, true, false, false, true,
-                      ConvAG>, 64, 128);
-  } else if (M >= 128) {
-    launch(GemmBf16NT<2, 2, 4, 2, false, true, true, false, false, true,
-                      ConvAG>, 128, 64);
-  } else {
-    launch(GemmBf16NT<2, 2, 2, 2, false, true, true, false, false, true,
-                      ConvAG>, 64, 64);
-  }
-  return hipGetLastError();
+extern "C" hipError_t stf_conv2d_fwd_nt(const void* x, const void* w, void* y,
+                                        const void* zero16,
+                                        const StfConvGeom* g, int64_t rscp,
+                                        hipStream_t stream) {
+  if ((g->c % 8) != 0) return hipErrorInvalidValue;
+  ConvAG ag = MakeConvAG(*g, x, zero16);
+  int64_t M = (int64_t)g->n * g->p * g->q;
+  return LaunchNT<Path::kConvFwd, false, true>(
+      ag, w, y, M, g->cout, rscp, g->cout, 1, false, stream);
 }
-

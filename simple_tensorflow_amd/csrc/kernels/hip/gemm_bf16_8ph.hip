@@ -25,6 +25,9 @@
 //   ph4: glds B-piece1(u+2) (BN=256 only); s_waitcnt vmcnt(B loads of u+2)
 //        — everything tile u+1 needs has landed, B(u+2) stays in flight.
 #include "hip_common.h"
+#include "stf_kernels.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -271,6 +274,30 @@ __launch_bounds__(512) __global__ void Gemm256x8Ph(
   }
 }
 
+// Host launcher for either address generator: bf16 output, no bias, no ReLU
+// (all any caller asks for). OUT_BF16/FUSE_RELU and the bias argument stay
+// in the kernel: removing them would change tuned device code and needs GPU
+// timing. Caller has checked stf_gemm_bf16_8ph_ok(M, N, K).
+template <class AG>
+hipError_t Launch8Ph(const AG& ag, const void* B, void* C, const void* side,
+                     int64_t M, int64_t N, int64_t K, int64_t ldb,
+                     hipStream_t stream) {
+  auto launch = [&](auto nr_c) {
+    constexpr int NR = decltype(nr_c)::value;
+    int64_t blocks = (M / kBM) * (N / (64 * NR));
+    // LDS: A ring 64 KiB + B ring 2 * (BN*64*2) bytes.
+    size_t shmem = 64 * 1024 + 2 * (size_t)(64 * NR) * kBK * 2;
+    hipLaunchKernelGGL((Gemm256x8Ph<NR, true, false, AG>),
+                       dim3((uint32_t)blocks), dim3(kThreads), shmem, stream,
+                       ag, (const uint16_t*)B, C, (const float*)nullptr,
+                       (const uint16_t*)side, M, N, K, ldb);
+  };
+  if (N % 256 == 0) launch(std::integral_constant<int, 4>{});
+  else if (N % 128 == 0) launch(std::integral_constant<int, 2>{});
+  else launch(std::integral_constant<int, 1>{});
+  return hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,48 +308,12 @@ int stf_gemm_bf16_8ph_ok(int64_t M, int64_t N, int64_t K) {
 }
 
 hipError_t stf_gemm_bf16_8ph_side(const void* A, const void* B, void* C,
-                                  const void* bias_f32, const void* side_bf16,
-                                  int64_t M, int64_t N, int64_t K, int64_t lda,
-                                  int64_t ldb, int out_bf16, int fuse_relu,
+                                  const void* side_bf16, int64_t M, int64_t N,
+                                  int64_t K, int64_t lda, int64_t ldb,
                                   hipStream_t stream) {
   if (!stf_gemm_bf16_8ph_ok(M, N, K)) return hipErrorInvalidValue;
   LinearAG ag{(const uint16_t*)A, lda};
-  const uint16_t* b = (const uint16_t*)B;
-  const float* bias = (const float*)bias_f32;
-  const uint16_t* side = (const uint16_t*)side_bf16;
-  int nr = (N % 256 == 0) ? 4 : (N % 128 == 0) ? 2 : 1;
-  int64_t blocks = (M / kBM) * (N / (64 * nr));
-  // LDS: A ring 64 KiB + B ring 2 * (BN*64*2) bytes.
-  size_t shmem = 64 * 1024 + 2 * (size_t)(64 * nr) * kBK * 2;
-#define STF_8PH_LAUNCH(NR_, OB, FR)                                          \
-  hipLaunchKernelGGL((Gemm256x8Ph<NR_, OB, FR, LinearAG>),                   \
-                     dim3((uint32_t)blocks), dim3(kThreads), shmem, stream,  \
-                     ag, b, C, bias, side, M, N, K, ldb)
-#define STF_8PH_NR(NR_)                                                      \
-  do {                                                                       \
-    if (out_bf16) {                                                          \
-      if (fuse_relu) STF_8PH_LAUNCH(NR_, true, true);                        \
-      else STF_8PH_LAUNCH(NR_, true, false);                                 \
-    } else {                                                                 \
-      if (fuse_relu) STF_8PH_LAUNCH(NR_, false, true);                       \
-      else STF_8PH_LAUNCH(NR_, false, false);                                \
-    }                                                                        \
-  } while (0)
-  if (nr == 4) STF_8PH_NR(4);
-  else if (nr == 2) STF_8PH_NR(2);
-  else STF_8PH_NR(1);
-#undef STF_8PH_NR
-#undef STF_8PH_LAUNCH
-  return hipGetLastError();
-}
-
-hipError_t stf_gemm_bf16_8ph(const void* A, const void* B, void* C,
-                             const void* bias_f32, int64_t M, int64_t N,
-                             int64_t K, int64_t lda, int64_t ldb,
-                             int out_bf16, int fuse_relu,
-                             hipStream_t stream) {
-  return stf_gemm_bf16_8ph_side(A, B, C, bias_f32, nullptr, M, N, K, lda,
-                                ldb, out_bf16, fuse_relu, stream);
+  return Launch8Ph(ag, B, C, side_bf16, M, N, K, ldb, stream);
 }
 
 // Implicit-GEMM Conv2D forward: y[M=NPQ, N=Cout] = im2col(x) * wt[Cout,rscp]^T
@@ -331,49 +322,13 @@ hipError_t stf_gemm_bf16_8ph(const void* A, const void* B, void* C,
 // (conv_ops.cc:664 ThenConvolveWithAlgorithm). Requires C%8==0 (16B loads
 // stay within one (r,s) patch) and the 8-phase geometry gate.
 hipError_t stf_conv2d_fwd_8ph(const void* x, const void* wt, void* y,
-                              const void* bias_f32, const void* zero16,
-                              int n, int h, int w, int c, int r, int s_,
-                              int sh, int sw, int ph, int pw, int p, int q,
-                              int64_t cout, int64_t rscp, int out_bf16,
-                              int fuse_relu, hipStream_t stream) {
-  int64_t M = (int64_t)n * p * q;
-  if (!stf_gemm_bf16_8ph_ok(M, cout, rscp) || (c % 8) != 0)
+                              const void* zero16, const StfConvGeom* g,
+                              int64_t rscp, hipStream_t stream) {
+  int64_t M = (int64_t)g->n * g->p * g->q;
+  if (!stf_gemm_bf16_8ph_ok(M, g->cout, rscp) || (g->c % 8) != 0)
     return hipErrorInvalidValue;
-  ConvAG ag;
-  ag.x = (const uint16_t*)x;
-  ag.zero16 = (const uint16_t*)zero16;
-  ag.div_pq.init((uint32_t)(p * q));
-  ag.div_q.init((uint32_t)q);
-  ag.div_c.init((uint32_t)c);
-  ag.div_s.init((uint32_t)s_);
-  ag.H = h; ag.W = w; ag.C = c; ag.S = s_;
-  ag.sh = sh; ag.sw = sw; ag.ph = ph; ag.pw = pw;
-  ag.rsc = (int64_t)r * s_ * c;
-  const uint16_t* b = (const uint16_t*)wt;
-  const float* bias = (const float*)bias_f32;
-  int nr = (cout % 256 == 0) ? 4 : (cout % 128 == 0) ? 2 : 1;
-  int64_t blocks = (M / kBM) * (cout / (64 * nr));
-  size_t shmem = 64 * 1024 + 2 * (size_t)(64 * nr) * kBK * 2;
-#define STF_C8_LAUNCH(NR_, OB, FR)                                           \
-  hipLaunchKernelGGL((Gemm256x8Ph<NR_, OB, FR, ConvAG>),                     \
-                     dim3((uint32_t)blocks), dim3(kThreads), shmem, stream,  \
-                     ag, b, y, bias, nullptr, M, cout, rscp, rscp)
-#define STF_C8_NR(NR_)                                                       \
-  do {                                                                       \
-    if (out_bf16) {                                                          \
-      if (fuse_relu) STF_C8_LAUNCH(NR_, true, true);                         \
-      else STF_C8_LAUNCH(NR_, true, false);                                  \
-    } else {                                                                 \
-      if (fuse_relu) STF_C8_LAUNCH(NR_, false, true);                        \
-      else STF_C8_LAUNCH(NR_, false, false);                                 \
-    }                                                                        \
-  } while (0)
-  if (nr == 4) STF_C8_NR(4);
-  else if (nr == 2) STF_C8_NR(2);
-  else STF_C8_NR(1);
-#undef STF_C8_NR
-#undef STF_C8_LAUNCH
-  return hipGetLastError();
+  return Launch8Ph(MakeConvAG(*g, x, zero16), wt, y, nullptr, M, g->cout,
+                   rscp, rscp, stream);
 }
 
 }  // extern "C"

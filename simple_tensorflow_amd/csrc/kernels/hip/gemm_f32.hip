@@ -2,6 +2,7 @@
 // f32 matmuls are off the bf16 hot path (guide §3: f32 peak is 157 TF either
 // way); this straightforward 64x64-tile kernel keeps f32 graphs on-device.
 #include "hip_common.h"
+#include "stf_kernels.h"
 
 namespace {
 

@@ -10,6 +10,8 @@
 
 #include <cstdint>
 
+#include "stf_kernels.h"
+
 #define STF_WAVE 64
 #define STF_NUM_XCD 8
 #define STF_NUM_CU 256
@@ -122,3 +124,19 @@ struct ConvAG {
     return x + ((((int64_t)n * H + h) * W + w) * C + c);
   }
 };
+
+// Host-side ConvAG setup shared by the implicit-GEMM conv entries.
+inline ConvAG MakeConvAG(const StfConvGeom& g, const void* x,
+                         const void* zero16) {
+  ConvAG ag;
+  ag.x = (const uint16_t*)x;
+  ag.zero16 = (const uint16_t*)zero16;
+  ag.div_pq.init((uint32_t)(g.p * g.q));
+  ag.div_q.init((uint32_t)g.q);
+  ag.div_c.init((uint32_t)g.c);
+  ag.div_s.init((uint32_t)g.s);
+  ag.H = g.h; ag.W = g.w; ag.C = g.c; ag.S = g.s;
+  ag.sh = g.sh; ag.sw = g.sw; ag.ph = g.ph; ag.pw = g.pw;
+  ag.rsc = (int64_t)g.r * g.s * g.c;
+  return ag;
+}

@@ -4,6 +4,7 @@
 // fused_batch_norm_op, maxpooling_op_gpu, avgpooling_op_gpu — redesigned for
 // wave64 + LDS per the CDNA4 guide, not translated.)
 #include "hip_common.h"
+#include "stf_kernels.h"
 
 namespace {
 

@@ -1,0 +1,224 @@
+// The C ABI between the host op layer (kernels/gpu_*.cc, rccl/rccl_ops.cc)
+// and the HIP kernel files (kernels/hip/*.hip). Every extern "C" stf_* entry
+// point is declared here exactly once; both the defining .hip file and every
+// caller include this header, so a signature drift is a compile error instead
+// of silently corrupted arguments at run time.
+//
+// Conventions: dtype codes are 0 = f32, 1 = bf16 (stf_cast: 0 f32, 1 bf16,
+// 2 f16, 3 i32, 4 i64, 5 bool); all launches are asynchronous on `stream`.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+// Conv2D geometry, NHWC input / RSCK filter. p,q = output height/width.
+struct StfConvGeom {
+  int n, h, w, c;
+  int r, s;
+  int sh, sw, ph, pw;
+  int p, q;
+  int64_t cout;
+};
+
+extern "C" {
+
+// ---- gemm_bf16.hip / gemm_bf16_8ph.hip / gemm_f32.hip ----
+// C[M,N] bf16 = A * B^T. a_km/b_km: operand stored contraction-major
+// ([K,M] / [K,N]); lda/ldb are the row strides of the stored layouts.
+hipError_t stf_gemm_bf16(const void* A, const void* B, void* C, int64_t M,
+                         int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                         int a_km, int b_km, hipStream_t stream);
+// NT shorthand: A [M,K], B [N,K], lda = ldb = K.
+hipError_t stf_gemm_bf16_nt(const void* A, const void* B, void* C, int64_t M,
+                            int64_t N, int64_t K, hipStream_t stream);
+// Atomically accumulates into a pre-zeroed f32 C.
+hipError_t stf_gemm_bf16_splitk(const void* A, const void* B, void* C_f32,
+                                int64_t M, int64_t N, int64_t K, int64_t lda,
+                                int64_t ldb, int a_km, int b_km, int splitk,
+                                hipStream_t stream);
+int stf_gemm_bf16_8ph_ok(int64_t M, int64_t N, int64_t K);
+// 8-phase NT GEMM, bf16 out; side_bf16 (optional [M,N]) is added in the
+// epilogue.
+hipError_t stf_gemm_bf16_8ph_side(const void* A, const void* B, void* C,
+                                  const void* side_bf16, int64_t M, int64_t N,
+                                  int64_t K, int64_t lda, int64_t ldb,
+                                  hipStream_t stream);
+hipError_t stf_gemm_f32_nt(const void* A, const void* B, void* C, int64_t M,
+                           int64_t N, int64_t K, hipStream_t stream);
+
+// ---- implicit-GEMM conv (gemm_bf16*.hip) and im2col (conv_im2col.hip) ----
+// zero16: >= 16 zeroed device bytes (padding loads). rscp: K extent of the
+// weight matrix (r*s*c rounded up to 64).
+hipError_t stf_conv2d_fwd_8ph(const void* x, const void* wt, void* y,
+                              const void* zero16, const StfConvGeom* g,
+                              int64_t rscp, hipStream_t stream);
+hipError_t stf_conv2d_fwd_nt(const void* x, const void* w, void* y,
+                             const void* zero16, const StfConvGeom* g,
+                             int64_t rscp, hipStream_t stream);
+hipError_t stf_conv2d_dw_splitk(const void* x, const void* dy, void* dw_f32,
+                                const void* zero16, const StfConvGeom* g,
+                                int splitk, hipStream_t stream);
+hipError_t stf_im2col_bf16(const void* x, void* col, const StfConvGeom* g,
+                           int64_t ld, hipStream_t stream);
+hipError_t stf_col2im_bf16(const void* dcol, void* dx, const StfConvGeom* g,
+                           hipStream_t stream);
+
+// ---- depthwise.hip ----
+hipError_t stf_depthwise_fwd(const void* x, const void* w, void* y, int N,
+                             int H, int W, int C, int R, int S, int sh, int sw,
+                             int ph, int pw, int P, int Q, int mult,
+                             hipStream_t stream);
+hipError_t stf_depthwise_bwd_input(const void* dy, const void* w, void* dx,
+                                   int N, int H, int W, int C, int R, int S,
+                                   int sh, int sw, int ph, int pw, int P,
+                                   int Q, int mult, hipStream_t stream);
+hipError_t stf_depthwise_bwd_filter(const void* x, const void* dy,
+                                    float* dw_f32, int N, int H, int W, int C,
+                                    int R, int S, int sh, int sw, int ph,
+                                    int pw, int P, int Q, int mult,
+                                    hipStream_t stream);
+
+// ---- elementwise.hip ----
+hipError_t stf_unary(int op, int dtype, const void* x, void* y, int64_t n,
+                     hipStream_t stream);
+hipError_t stf_binary(int op, int dtype, const void* a, const void* b,
+                      void* y, int64_t n, hipStream_t stream);
+hipError_t stf_binary_scalar(int op, int dtype, const void* a,
+                             const void* scalar, void* y, int64_t n,
+                             int scalar_left, hipStream_t stream);
+hipError_t stf_binary_bcast(int op, int dtype, const void* a, const void* b,
+                            void* y, int64_t n, int rank,
+                            const int64_t* out_dims, const int64_t* sa,
+                            const int64_t* sb, hipStream_t stream);
+hipError_t stf_cast(int sdt, int ddt, const void* x, void* y, int64_t n,
+                    hipStream_t stream);
+// Casts f32 -> bf16 and re-zeroes the source (split-K arena drain).
+hipError_t stf_cast_f32_bf16_zero(void* src_f32, void* dst_bf16, int64_t n,
+                                  hipStream_t stream);
+hipError_t stf_fill_f32(void* y, float v, int64_t n, int as_bf16,
+                        hipStream_t stream);
+hipError_t stf_scale(int dtype, const void* x, void* y, int64_t n,
+                     float factor, hipStream_t stream);
+hipError_t stf_fused_elementwise(int dtype, const void** inputs,
+                                 const uint8_t* scalar_flags, int n_in,
+                                 const int64_t* prog, int n_prog, void* out,
+                                 int64_t n, hipStream_t stream);
+
+// ---- lrn.hip ----
+hipError_t stf_lrn_fwd(const void* x, void* y, int64_t rows, int c,
+                       int radius, float bias, float alpha, float beta,
+                       hipStream_t stream);
+
+// ---- nn_kernels.hip ----
+hipError_t stf_bias_add(int dtype, const void* x, const void* bias, void* y,
+                        int64_t n, int c, hipStream_t stream);
+hipError_t stf_bias_grad(int dtype, const void* dy, void* db_f32,
+                         int64_t rows, int c, hipStream_t stream);
+hipError_t stf_softmax(int dtype, int log_sm, const void* x, void* y,
+                       int64_t rows, int cols, hipStream_t stream);
+hipError_t stf_sparse_xent(int dtype, const void* logits, const void* labels,
+                           int labels_i32, void* loss_f32, void* backprop,
+                           int64_t rows, int cols, hipStream_t stream);
+hipError_t stf_xent(int dtype, const void* logits, const void* labels,
+                    void* loss_f32, void* backprop, int64_t rows, int cols,
+                    hipStream_t stream);
+hipError_t stf_bn_fwd(int dtype, const void* x, const void* scale,
+                      const void* offset, float* acc, float* mean, float* var,
+                      float* inv_std, void* y, int64_t rows, int c, float eps,
+                      int fuse_relu, hipStream_t stream);
+hipError_t stf_bn_stats_only(int dtype, const void* x, float* acc,
+                             float* mean, float* var, float* inv_std,
+                             int64_t rows, int c, float eps,
+                             hipStream_t stream);
+hipError_t stf_bn_add_relu(const void* x, const void* side, const float* mean,
+                           const float* inv_std, const void* scale,
+                           const void* offset, void* y, int64_t n, int c,
+                           hipStream_t stream);
+hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
+                      const void* y_relu, const float* mean,
+                      const float* inv_std, const void* scale, float* sum_dy,
+                      float* sum_dy_xhat, void* dx, int64_t rows, int c,
+                      int fuse_relu, hipStream_t stream);
+hipError_t stf_pool_fwd(int dtype, int is_max, const void* x, void* y, int N,
+                        int H, int W, int C, int kh, int kw, int sh, int sw,
+                        int ph, int pw, int P, int Q, hipStream_t stream);
+hipError_t stf_max_pool_bwd(int dtype, const void* x, const void* dy,
+                            float* dx_f32, int N, int H, int W, int C, int kh,
+                            int kw, int sh, int sw, int ph, int pw, int P,
+                            int Q, hipStream_t stream);
+hipError_t stf_max_pool_bwd_v8(const void* x, const void* dy, void* dx_bf16,
+                               int N, int H, int W, int C, int kh, int kw,
+                               int sh, int sw, int ph, int pw, int P, int Q,
+                               hipStream_t stream);
+hipError_t stf_avg_pool_bwd(int dtype, const void* dy, void* dx, int N, int H,
+                            int W, int C, int kh, int kw, int sh, int sw,
+                            int ph, int pw, int P, int Q, hipStream_t stream);
+hipError_t stf_lstm_gates(int dtype, const void* gates, const void* c_prev,
+                          float forget_bias, void* i_out, void* f_out,
+                          void* o_out, void* ci_out, void* cs_out,
+                          void* co_out, void* h_out, int64_t batch, int H,
+                          hipStream_t stream);
+hipError_t stf_lstm_gates_grad(int dtype, const void* c_prev, const void* i_,
+                               const void* f_, const void* o_,
+                               const void* ci_, const void* co_,
+                               const void* dh, const void* dcs_next,
+                               void* dgates, void* dc_prev, int64_t batch,
+                               int H, hipStream_t stream);
+
+// ---- transform.hip ----
+hipError_t stf_transpose2d(int elem_size, const void* in, void* out,
+                           int64_t rows, int64_t cols, hipStream_t stream);
+hipError_t stf_permute(int elem_size, const void* in, void* out, int64_t n,
+                       int rank, const int64_t* out_dims,
+                       const int64_t* src_strides, hipStream_t stream);
+hipError_t stf_bcast_copy(int elem_size, const void* in, void* out, int64_t n,
+                          int rank, const int64_t* out_dims,
+                          const int64_t* src_strides, hipStream_t stream);
+hipError_t stf_block_pad(int dtype, const void* src, void* dst,
+                         int64_t nblocks, int64_t in_block, int64_t out_block,
+                         hipStream_t stream);
+hipError_t stf_l2loss(int dtype, const void* x, float* out_f32, int64_t n,
+                      hipStream_t stream);
+hipError_t stf_full_reduce(int dtype, int red, const void* x, float* out_f32,
+                           int64_t n, hipStream_t stream);
+hipError_t stf_row_reduce(int dtype, int red, const void* x, float* y,
+                          int64_t rows, int64_t inner, hipStream_t stream);
+hipError_t stf_col_reduce(int dtype, int red, const void* x, float* y,
+                          int64_t outer, int64_t inner, hipStream_t stream);
+hipError_t stf_apply_sgd(int grad_bf16, void* var, const void* lr,
+                         const void* grad, int64_t n, hipStream_t stream);
+hipError_t stf_apply_momentum(int grad_bf16, void* var, void* accum,
+                              const void* lr, const void* grad,
+                              const void* momentum, int nesterov, int64_t n,
+                              hipStream_t stream);
+hipError_t stf_apply_adam(int grad_bf16, void* var, void* m, void* v,
+                          const void* b1p, const void* b2p, const void* lr,
+                          const void* b1, const void* b2, const void* eps,
+                          const void* grad, int64_t n, hipStream_t stream);
+hipError_t stf_strided_copy(int elem_size, int scatter, const void* src,
+                            void* dst, int64_t outer, int64_t rows,
+                            int64_t inner, int64_t big_stride,
+                            int64_t row_off, hipStream_t stream);
+hipError_t stf_gather_rows(int dtype, int idx_i32, const void* params,
+                           const void* indices, void* out, int64_t nidx,
+                           int64_t row, int64_t nrows, hipStream_t stream);
+hipError_t stf_segment_sum(int dtype, int idx_i32, const void* data,
+                           const void* ids, float* out_f32, int64_t nidx,
+                           int64_t row, int64_t nseg, hipStream_t stream);
+hipError_t stf_random_uniform(uint64_t seed, void* ctr_dev, void* out,
+                              int64_t n, int as_bf16, hipStream_t stream);
+hipError_t stf_random_normal(uint64_t seed, void* ctr_dev, void* out,
+                             int64_t n, int as_bf16, int truncated,
+                             hipStream_t stream);
+
+// ---- comm_pack.hip ----
+int stf_comm_max_segments();
+hipError_t stf_comm_pack(int nseg, const void* const* ptrs,
+                         const int64_t* ends, const unsigned char* is_bf16,
+                         float* dst, int64_t total, hipStream_t stream);
+hipError_t stf_comm_unpack(int nseg, void* const* ptrs, const int64_t* ends,
+                           const unsigned char* is_bf16, const float* src,
+                           float scale, int64_t total, hipStream_t stream);
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 // reduction_ops_gpu, tile_ops_gpu, training_ops_gpu, random_op_gpu —
 // wave64-native designs.)
 #include "hip_common.h"
+#include "stf_kernels.h"
 
 #include "../philox.h"
 

@@ -30,17 +30,8 @@
 #include <mutex>
 #include <vector>
 
+#include "kernels/hip/stf_kernels.h"
 #include "kernels/kernel_util.h"
-
-extern "C" {
-int stf_comm_max_segments();
-hipError_t stf_comm_pack(int nseg, const void* const* ptrs,
-                         const int64_t* ends, const unsigned char* is_bf16,
-                         float* dst, int64_t total, hipStream_t stream);
-hipError_t stf_comm_unpack(int nseg, void* const* ptrs, const int64_t* ends,
-                           const unsigned char* is_bf16, const float* src,
-                           float scale, int64_t total, hipStream_t stream);
-}
 
 namespace stf {
 

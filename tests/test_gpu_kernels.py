@@ -152,6 +152,72 @@ def test_conv2d_grads_vs_cpu():
     np.testing.assert_allclose(gdw, cdw, rtol=3e-2, atol=0.3)
 
 
+# One case per Conv2D dispatch path: GPU bf16 vs the CPU f32 kernels on the
+# same bf16-rounded values.
+def _conv_out_shape(shape, filt, stride, padding):
+    n, h, w, _ = shape
+    r, s, _, k = filt
+    if padding == 'SAME':
+        return (n, -(-h // stride), -(-w // stride), k)
+    return (n, (h - r) // stride + 1, (w - s) // stride + 1, k)
+
+
+def _conv_gpu_vs_cpu(op, shape, filt, stride, padding):
+    rng = np.random.RandomState(9)
+    x = _bf16(rng.randn(*shape) * 0.5)
+    w = _bf16(rng.randn(*filt) * 0.2)
+    dy = _bf16(rng.randn(*_conv_out_shape(shape, filt, stride, padding)) * 0.1)
+    strides = [1, stride, stride, 1]
+
+    def build(dtype):
+        xt, wt, dyt = (tf.constant(v, dtype=dtype) for v in (x, w, dy))
+        if op == 'fwd':
+            return tf.nn.conv2d(xt, wt, strides, padding)
+        if op == 'dw':
+            return tf.nn.conv2d_backprop_filter(xt, list(filt), dyt, strides,
+                                                padding)
+        return tf.nn.conv2d_backprop_input(list(shape), wt, dyt, strides,
+                                           padding)
+
+    with _sess() as s:
+        gpu = build(tf.bfloat16)
+        with tf.device('/cpu:0'):
+            cpu = build(tf.float32)
+        return s.run([gpu, cpu])
+
+
+@pytest.mark.parametrize('shape,filt,stride,padding', [
+    ((1, 16, 16, 8), (3, 3, 8, 64), 1, 'SAME'),   # implicit 8-phase (M=256)
+    ((2, 16, 16, 8), (1, 1, 8, 16), 2, 'SAME'),   # strided 1x1: implicit NT
+    ((2, 9, 9, 8), (3, 3, 8, 12), 1, 'SAME'),     # cout%8!=0: im2col + w^T
+    ((2, 12, 12, 8), (3, 3, 8, 16), 1, 'VALID'),  # VALID padding
+])
+def test_conv2d_fwd_paths(shape, filt, stride, padding):
+    out, ref = _conv_gpu_vs_cpu('fwd', shape, filt, stride, padding)
+    assert out.shape == _conv_out_shape(shape, filt, stride, padding)
+    np.testing.assert_allclose(out, ref, rtol=3e-2, atol=0.15)
+
+
+@pytest.mark.parametrize('shape,filt,stride,padding', [
+    ((1, 8, 8, 8), (3, 3, 8, 16), 1, 'SAME'),     # implicit dW, M=64, split 1
+    ((4, 16, 16, 8), (3, 3, 8, 16), 1, 'SAME'),   # implicit dW, split 2, arena
+    ((1, 16, 16, 3), (7, 7, 3, 8), 2, 'SAME'),    # stem channel-pad + unpad
+    ((2, 10, 10, 8), (1, 1, 8, 16), 1, 'SAME'),   # 1x1 K-major direct
+    ((2, 9, 9, 8), (3, 3, 8, 12), 1, 'SAME'),     # cout%8!=0: im2col fallback
+])
+def test_conv2d_dw_paths(shape, filt, stride, padding):
+    out, ref = _conv_gpu_vs_cpu('dw', shape, filt, stride, padding)
+    assert out.shape == filt
+    np.testing.assert_allclose(out, ref, rtol=3e-2, atol=0.3)
+
+
+def test_conv2d_dx_strided_col2im():
+    shape = (2, 17, 17, 8)
+    out, ref = _conv_gpu_vs_cpu('dx', shape, (3, 3, 8, 16), 2, 'SAME')
+    assert out.shape == shape
+    np.testing.assert_allclose(out, ref, rtol=3e-2, atol=0.1)
+
+
 # ---------------------------------------------------------------------------
 # batch norm / softmax / xent
 # ---------------------------------------------------------------------------

@@ -609,7 +609,7 @@ class LRNOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("LRN").Device(DEVICE_CPU), LRNOp);
 
 // ------------------------- fused LSTM cell pointwise ------------------------
-// CPU reference of the GPU LstmGates kernels (nn_kernels.hip); gate order
+// CPU reference of the GPU LstmGates kernels (hip/lstm.hip); gate order
 // i, j, f, o as produced by BasicLSTMCell's single [B, 4H] GEMM.
 template <typename T>
 class LSTMGatesOp : public OpKernel {

@@ -183,8 +183,8 @@ class GpuBatchNormAddReluMiOp : public OpKernel {
     OP_HIP_OK(ctx, stf_bn_add_relu(x.raw_data(), side.raw_data(),
                                    mean->flat<float>(),
                                    inv_std->flat<float>(), scale.raw_data(),
-                                   offset.raw_data(), y->raw_data(),
-                                   rows * (int64_t)c, c, s));
+                                   offset.raw_data(), y->raw_data(), rows, c,
+                                   s));
   }
 
  private:
@@ -273,21 +273,28 @@ static void GetPool(OpKernelConstruction* c, PoolAttrs* p) {
   c->GetAttr("strides", &p->strides);
   c->GetAttr("padding", &p->padding);
 }
-static void PoolDims(const TensorShape& x, const PoolAttrs& p, int64_t* P,
-                     int64_t* Q, int64_t* ph, int64_t* pw) {
-  int64_t H = x.dim_size(1), W = x.dim_size(2);
-  int64_t kh = p.ksize[1], kw = p.ksize[2], sh = p.strides[1],
-          sw = p.strides[2];
+// Geometry of pooling an NHWC input of shape x, as the HIP entries take it.
+static StfPoolGeom PoolGeomFor(const TensorShape& x, const PoolAttrs& p) {
+  StfPoolGeom g;
+  g.N = (int)x.dim_size(0);
+  g.H = (int)x.dim_size(1);
+  g.W = (int)x.dim_size(2);
+  g.C = (int)x.dim_size(3);
+  g.kh = (int)p.ksize[1];
+  g.kw = (int)p.ksize[2];
+  g.sh = (int)p.strides[1];
+  g.sw = (int)p.strides[2];
   if (p.padding == "SAME") {
-    *P = (H + sh - 1) / sh;
-    *Q = (W + sw - 1) / sw;
-    *ph = std::max<int64_t>(0, (*P - 1) * sh + kh - H) / 2;
-    *pw = std::max<int64_t>(0, (*Q - 1) * sw + kw - W) / 2;
+    g.P = (g.H + g.sh - 1) / g.sh;
+    g.Q = (g.W + g.sw - 1) / g.sw;
+    g.ph = std::max(0, (g.P - 1) * g.sh + g.kh - g.H) / 2;
+    g.pw = std::max(0, (g.Q - 1) * g.sw + g.kw - g.W) / 2;
   } else {
-    *P = (H - kh) / sh + 1;
-    *Q = (W - kw) / sw + 1;
-    *ph = *pw = 0;
+    g.P = (g.H - g.kh) / g.sh + 1;
+    g.Q = (g.W - g.kw) / g.sw + 1;
+    g.ph = g.pw = 0;
   }
+  return g;
 }
 
 class GpuPoolOp : public OpKernel {
@@ -298,17 +305,10 @@ class GpuPoolOp : public OpKernel {
   }
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
-    int64_t P, Q, ph, pw;
-    PoolDims(x.shape(), p_, &P, &Q, &ph, &pw);
-    Tensor* y = ctx->allocate_output(
-        0, TensorShape({x.dim_size(0), P, Q, x.dim_size(3)}));
+    StfPoolGeom g = PoolGeomFor(x.shape(), p_);
+    Tensor* y = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.C}));
     OP_HIP_OK(ctx, stf_pool_fwd(DtypeCode(x.dtype()), is_max_, x.raw_data(),
-                                y->raw_data(), (int)x.dim_size(0),
-                                (int)x.dim_size(1), (int)x.dim_size(2),
-                                (int)x.dim_size(3), (int)p_.ksize[1],
-                                (int)p_.ksize[2], (int)p_.strides[1],
-                                (int)p_.strides[2], (int)ph, (int)pw, (int)P,
-                                (int)Q, GPU_STREAM(ctx)));
+                                y->raw_data(), &g, GPU_STREAM(ctx)));
   }
 
  private:
@@ -336,30 +336,20 @@ class GpuMaxPoolGradOp : public OpKernel {
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& dy = ctx->input(2);
-    int64_t P, Q, ph, pw;
-    PoolDims(x.shape(), p_, &P, &Q, &ph, &pw);
+    StfPoolGeom g = PoolGeomFor(x.shape(), p_);
     Tensor* dx = ctx->allocate_output(0, x.shape());
     hipStream_t s = GPU_STREAM(ctx);
-    if (x.dtype() == DT_BFLOAT16 && x.dim_size(3) % 8 == 0) {
+    if (x.dtype() == DT_BFLOAT16 && g.C % 8 == 0) {
       // per-input direct path: no f32 scratch, no zero fill, no cast
-      OP_HIP_OK(ctx, stf_max_pool_bwd_v8(
-                         x.raw_data(), dy.raw_data(), dx->raw_data(),
-                         (int)x.dim_size(0), (int)x.dim_size(1),
-                         (int)x.dim_size(2), (int)x.dim_size(3),
-                         (int)p_.ksize[1], (int)p_.ksize[2],
-                         (int)p_.strides[1], (int)p_.strides[2], (int)ph,
-                         (int)pw, (int)P, (int)Q, s));
+      OP_HIP_OK(ctx, stf_max_pool_bwd_v8(x.raw_data(), dy.raw_data(),
+                                         dx->raw_data(), &g, s));
       return;
     }
     Tensor scratch = ctx->allocate_temp(DT_FLOAT, x.shape());
     OP_HIP_OK(ctx, ZeroF32(scratch.raw_data(), x.NumElements(), s));
     OP_HIP_OK(ctx, stf_max_pool_bwd(DtypeCode(x.dtype()), x.raw_data(),
-                                    dy.raw_data(), scratch.flat<float>(),
-                                    (int)x.dim_size(0), (int)x.dim_size(1),
-                                    (int)x.dim_size(2), (int)x.dim_size(3),
-                                    (int)p_.ksize[1], (int)p_.ksize[2],
-                                    (int)p_.strides[1], (int)p_.strides[2],
-                                    (int)ph, (int)pw, (int)P, (int)Q, s));
+                                    dy.raw_data(), scratch.flat<float>(), &g,
+                                    s));
     OP_HIP_OK(ctx, stf_cast(0, CastCode(dx->dtype()), scratch.raw_data(),
                             dx->raw_data(), x.NumElements(), s));
   }
@@ -379,18 +369,10 @@ class GpuAvgPoolGradOp : public OpKernel {
     auto in_sizes = IntVector(ctx->input(0));
     const Tensor& dy = ctx->input(1);
     TensorShape x_shape(in_sizes);
-    int64_t P, Q, ph, pw;
-    PoolDims(x_shape, p_, &P, &Q, &ph, &pw);
+    StfPoolGeom g = PoolGeomFor(x_shape, p_);
     Tensor* dx = ctx->allocate_output(0, x_shape);
     OP_HIP_OK(ctx, stf_avg_pool_bwd(DtypeCode(dy.dtype()), dy.raw_data(),
-                                    dx->raw_data(), (int)x_shape.dim_size(0),
-                                    (int)x_shape.dim_size(1),
-                                    (int)x_shape.dim_size(2),
-                                    (int)x_shape.dim_size(3),
-                                    (int)p_.ksize[1], (int)p_.ksize[2],
-                                    (int)p_.strides[1], (int)p_.strides[2],
-                                    (int)ph, (int)pw, (int)P, (int)Q,
-                                    GPU_STREAM(ctx)));
+                                    dx->raw_data(), &g, GPU_STREAM(ctx)));
   }
 
  private:
@@ -451,7 +433,7 @@ class GpuL2LossOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("L2Loss").Device(DEVICE_GPU).TypeConstraint<float>("T"), GpuL2LossOp);
 REGISTER_KERNEL_BUILDER(Name("L2Loss").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuL2LossOp);
 
-// Fused LSTM cell pointwise (nn_kernels.hip LstmGatesKernel); one launch
+// Fused LSTM cell pointwise (hip/lstm.hip LstmGatesKernel); one launch
 // replaces the composed cell's ~17 elementwise/split launches per timestep.
 class GpuLSTMGatesOp : public OpKernel {
  public:

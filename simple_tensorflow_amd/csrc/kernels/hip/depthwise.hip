@@ -102,15 +102,18 @@ __global__ void DwBwdFilterKernel(const __bf16* __restrict__ x,
   }
 }
 
+DwGeom MakeDwGeom(const StfConvGeom& g, int mult) {
+  return DwGeom{g.n,  g.h,  g.w,  g.c, g.r, g.s, g.sh,
+                g.sw, g.ph, g.pw, g.p, g.q, mult};
+}
+
 }  // namespace
 
 extern "C" hipError_t stf_depthwise_fwd(const void* x, const void* w, void* y,
-                                        int N, int H, int W, int C, int R,
-                                        int S, int sh, int sw, int ph, int pw,
-                                        int P, int Q, int mult,
+                                        const StfConvGeom* cg, int mult,
                                         hipStream_t stream) {
-  DwGeom g{N, H, W, C, R, S, sh, sw, ph, pw, P, Q, mult};
-  int64_t total = (int64_t)N * P * Q * C * mult;
+  DwGeom g = MakeDwGeom(*cg, mult);
+  int64_t total = (int64_t)g.N * g.P * g.Q * g.C * mult;
   hipLaunchKernelGGL(DwFwdKernel, ElemwiseGrid(total, 256, 1), dim3(256), 0,
                      stream, (const __bf16*)x, (const __bf16*)w, (__bf16*)y,
                      g, total);
@@ -118,13 +121,10 @@ extern "C" hipError_t stf_depthwise_fwd(const void* x, const void* w, void* y,
 }
 
 extern "C" hipError_t stf_depthwise_bwd_input(const void* dy, const void* w,
-                                              void* dx, int N, int H, int W,
-                                              int C, int R, int S, int sh,
-                                              int sw, int ph, int pw, int P,
-                                              int Q, int mult,
-                                              hipStream_t stream) {
-  DwGeom g{N, H, W, C, R, S, sh, sw, ph, pw, P, Q, mult};
-  int64_t total = (int64_t)N * H * W * C;
+                                              void* dx, const StfConvGeom* cg,
+                                              int mult, hipStream_t stream) {
+  DwGeom g = MakeDwGeom(*cg, mult);
+  int64_t total = (int64_t)g.N * g.H * g.W * g.C;
   hipLaunchKernelGGL(DwBwdInputKernel, ElemwiseGrid(total, 256, 1), dim3(256),
                      0, stream, (const __bf16*)dy, (const __bf16*)w,
                      (__bf16*)dx, g, total);
@@ -132,13 +132,11 @@ extern "C" hipError_t stf_depthwise_bwd_input(const void* dy, const void* w,
 }
 
 extern "C" hipError_t stf_depthwise_bwd_filter(const void* x, const void* dy,
-                                               float* dw_f32, int N, int H,
-                                               int W, int C, int R, int S,
-                                               int sh, int sw, int ph, int pw,
-                                               int P, int Q, int mult,
+                                               float* dw_f32,
+                                               const StfConvGeom* cg, int mult,
                                                hipStream_t stream) {
-  DwGeom g{N, H, W, C, R, S, sh, sw, ph, pw, P, Q, mult};
-  int64_t total = (int64_t)N * P * Q * C * mult;
+  DwGeom g = MakeDwGeom(*cg, mult);
+  int64_t total = (int64_t)g.N * g.P * g.Q * g.C * mult;
   hipLaunchKernelGGL(DwBwdFilterKernel, ElemwiseGrid(total, 256, 1),
                      dim3(256), 0, stream, (const __bf16*)x,
                      (const __bf16*)dy, dw_f32, g, total);

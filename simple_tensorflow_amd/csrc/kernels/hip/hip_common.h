@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "stf_kernels.h"
 
@@ -51,7 +52,27 @@ __device__ __forceinline__ int XcdSwizzle(int bid, int nblocks) {
   return base + idx;
 }
 
-#define HIP_LAUNCH_CHECK()                                       \
+// Run-time dtype code / flag -> compile-time template argument. The callback
+// is a generic lambda; it receives a tag whose ::type is the element type
+// (dtype 0 = float, else __bf16), or std::true_type / std::false_type:
+//   DispatchDtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+//   DispatchBool(flag, [&](auto f) { constexpr bool F = decltype(f)::value;
+template <typename T>
+struct TypeTag {
+  using type = T;
+};
+template <typename F>
+inline void DispatchDtype(int dtype, F&& f) {
+  if (dtype == 0) f(TypeTag<float>{});
+  else f(TypeTag<__bf16>{});
+}
+template <typename F>
+inline void DispatchBool(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+#define HIP_LAUNCH_CHECK()                                      \
   do {                                                           \
     hipError_t _e = hipGetLastError();                           \
     if (_e != hipSuccess) return _e;                             \

@@ -21,6 +21,12 @@ struct StfConvGeom {
   int64_t cout;
 };
 
+// Pooling geometry, NHWC. P,Q = output height/width. Passed by value to the
+// pooling kernels.
+struct StfPoolGeom {
+  int N, H, W, C, kh, kw, sh, sw, ph, pw, P, Q;
+};
+
 extern "C" {
 
 // ---- gemm_bf16.hip / gemm_bf16_8ph.hip / gemm_f32.hip ----
@@ -65,19 +71,16 @@ hipError_t stf_col2im_bf16(const void* dcol, void* dx, const StfConvGeom* g,
                            hipStream_t stream);
 
 // ---- depthwise.hip ----
-hipError_t stf_depthwise_fwd(const void* x, const void* w, void* y, int N,
-                             int H, int W, int C, int R, int S, int sh, int sw,
-                             int ph, int pw, int P, int Q, int mult,
+// Filter is [r, s, c, mult]; g->cout is unused.
+hipError_t stf_depthwise_fwd(const void* x, const void* w, void* y,
+                             const StfConvGeom* g, int mult,
                              hipStream_t stream);
 hipError_t stf_depthwise_bwd_input(const void* dy, const void* w, void* dx,
-                                   int N, int H, int W, int C, int R, int S,
-                                   int sh, int sw, int ph, int pw, int P,
-                                   int Q, int mult, hipStream_t stream);
+                                   const StfConvGeom* g, int mult,
+                                   hipStream_t stream);
 hipError_t stf_depthwise_bwd_filter(const void* x, const void* dy,
-                                    float* dw_f32, int N, int H, int W, int C,
-                                    int R, int S, int sh, int sw, int ph,
-                                    int pw, int P, int Q, int mult,
-                                    hipStream_t stream);
+                                    float* dw_f32, const StfConvGeom* g,
+                                    int mult, hipStream_t stream);
 
 // ---- elementwise.hip ----
 hipError_t stf_unary(int op, int dtype, const void* x, void* y, int64_t n,
@@ -110,9 +113,10 @@ hipError_t stf_lrn_fwd(const void* x, void* y, int64_t rows, int c,
                        int radius, float bias, float alpha, float beta,
                        hipStream_t stream);
 
-// ---- nn_kernels.hip ----
+// ---- loss.hip ----
 hipError_t stf_bias_add(int dtype, const void* x, const void* bias, void* y,
                         int64_t n, int c, hipStream_t stream);
+// db_f32 must be zeroed.
 hipError_t stf_bias_grad(int dtype, const void* dy, void* db_f32,
                          int64_t rows, int c, hipStream_t stream);
 hipError_t stf_softmax(int dtype, int log_sm, const void* x, void* y,
@@ -123,37 +127,45 @@ hipError_t stf_sparse_xent(int dtype, const void* logits, const void* labels,
 hipError_t stf_xent(int dtype, const void* logits, const void* labels,
                     void* loss_f32, void* backprop, int64_t rows, int cols,
                     hipStream_t stream);
+
+// ---- bn.hip ----
+// x is [rows, c]. acc: zeroed f32 [2c]; mean/var/inv_std: f32 [c] outputs.
 hipError_t stf_bn_fwd(int dtype, const void* x, const void* scale,
                       const void* offset, float* acc, float* mean, float* var,
                       float* inv_std, void* y, int64_t rows, int c, float eps,
                       int fuse_relu, hipStream_t stream);
+// The statistics half of stf_bn_fwd (stf_bn_add_relu normalizes after it).
 hipError_t stf_bn_stats_only(int dtype, const void* x, float* acc,
                              float* mean, float* var, float* inv_std,
                              int64_t rows, int c, float eps,
                              hipStream_t stream);
+// y = relu(bn(x) + side); bf16 only, c % 8 == 0.
 hipError_t stf_bn_add_relu(const void* x, const void* side, const float* mean,
                            const float* inv_std, const void* scale,
-                           const void* offset, void* y, int64_t n, int c,
+                           const void* offset, void* y, int64_t rows, int c,
                            hipStream_t stream);
+// sum_dy (= doffset) and sum_dy_xhat (= dscale) are zeroed f32 [c] and are
+// accumulated in place.
 hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
                       const void* y_relu, const float* mean,
                       const float* inv_std, const void* scale, float* sum_dy,
                       float* sum_dy_xhat, void* dx, int64_t rows, int c,
                       int fuse_relu, hipStream_t stream);
-hipError_t stf_pool_fwd(int dtype, int is_max, const void* x, void* y, int N,
-                        int H, int W, int C, int kh, int kw, int sh, int sw,
-                        int ph, int pw, int P, int Q, hipStream_t stream);
+
+// ---- pool.hip ----
+hipError_t stf_pool_fwd(int dtype, int is_max, const void* x, void* y,
+                        const StfPoolGeom* g, hipStream_t stream);
+// dx_f32: zeroed scratch [N*H*W*C]; the caller casts it to the output dtype.
 hipError_t stf_max_pool_bwd(int dtype, const void* x, const void* dy,
-                            float* dx_f32, int N, int H, int W, int C, int kh,
-                            int kw, int sh, int sw, int ph, int pw, int P,
-                            int Q, hipStream_t stream);
+                            float* dx_f32, const StfPoolGeom* g,
+                            hipStream_t stream);
+// bf16, C % 8 == 0: writes dx directly, no scratch.
 hipError_t stf_max_pool_bwd_v8(const void* x, const void* dy, void* dx_bf16,
-                               int N, int H, int W, int C, int kh, int kw,
-                               int sh, int sw, int ph, int pw, int P, int Q,
-                               hipStream_t stream);
-hipError_t stf_avg_pool_bwd(int dtype, const void* dy, void* dx, int N, int H,
-                            int W, int C, int kh, int kw, int sh, int sw,
-                            int ph, int pw, int P, int Q, hipStream_t stream);
+                               const StfPoolGeom* g, hipStream_t stream);
+hipError_t stf_avg_pool_bwd(int dtype, const void* dy, void* dx,
+                            const StfPoolGeom* g, hipStream_t stream);
+
+// ---- lstm.hip ----
 hipError_t stf_lstm_gates(int dtype, const void* gates, const void* c_prev,
                           float forget_bias, void* i_out, void* f_out,
                           void* o_out, void* ci_out, void* cs_out,

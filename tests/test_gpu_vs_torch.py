@@ -301,3 +301,177 @@ def test_avg_pool_fwd_and_grad_vs_torch():
     assert np.abs(got_y - want_y).max() < 0.05
     denom = np.abs(want_g) + 0.1
     assert np.percentile(np.abs(got_g - want_g) / denom, 99) < 0.1
+
+
+# ---------------------------------------------------------------------------
+# Batch norm and pooling: every dispatch path (dtype x C%8 x fuse_relu), odd
+# row counts, and the multi-row V9 loop. Reference: CPU torch in f32 fed the
+# same (bf16-rounded where the op is bf16) inputs.
+# ---------------------------------------------------------------------------
+def _round_bf16(a):
+    return torch.from_numpy(a).bfloat16().float().numpy()
+
+
+def _grad_close_bf16(got, want, bound=0.15):
+    rel = np.abs(got - want) / (np.abs(want) + 0.1)
+    assert np.percentile(rel, 99) < bound
+
+
+def _bn_case(dtype, rows, C, fuse_relu, seed, with_side=False):
+    """Runs BatchNormMi (or BatchNormAddReluMi) forward + backward on the
+    GPU and in torch; returns (got, want) dicts of numpy arrays."""
+    from simple_tensorflow_amd.python.framework.ops import apply_op
+    rng = np.random.RandomState(seed)
+    bf16 = dtype == tf.bfloat16
+    rnd = _round_bf16 if bf16 else (lambda a: a)
+    x = rnd(rng.randn(rows, C).astype(np.float32))
+    side = rnd(rng.randn(rows, C).astype(np.float32))
+    wgt = rnd(rng.randn(rows, C).astype(np.float32))
+    scale = rng.rand(C).astype(np.float32) + 0.5
+    offset = rng.randn(C).astype(np.float32)
+
+    xt = tf.constant(x, dtype=dtype)
+    st, ot = tf.constant(scale), tf.constant(offset)
+    if with_side:
+        sdt = tf.constant(side, dtype=dtype)
+        y, mean, var, _ = apply_op('BatchNormAddReluMi', xt, st, ot, sdt,
+                                   epsilon=1e-4)
+        wrt = [xt, st, ot, sdt]
+    else:
+        y, mean, var, _ = apply_op('BatchNormMi', xt, st, ot, epsilon=1e-4,
+                                   fuse_relu=fuse_relu)
+        wrt = [xt, st, ot]
+    # fixed random weighting: grad(sum(y)) wrt x cancels to ~0 under BN
+    loss = tf.reduce_sum(tf.cast(y, tf.float32) * tf.constant(wgt))
+    grads = tf.gradients(loss, wrt)
+    out = _run([y, mean, var] + grads)
+    names = ['y', 'mean', 'var', 'dx', 'dscale', 'doffset', 'dside']
+    got = dict(zip(names, out))
+
+    tx = torch.from_numpy(x).requires_grad_(True)
+    ts = torch.from_numpy(scale).requires_grad_(True)
+    to = torch.from_numpy(offset).requires_grad_(True)
+    tsd = torch.from_numpy(side).requires_grad_(True)
+    ty = torch.nn.functional.batch_norm(tx, None, None, ts, to,
+                                        training=True, eps=1e-4)
+    if with_side:
+        ty = torch.relu(ty + tsd)
+    elif fuse_relu:
+        ty = torch.relu(ty)
+    (ty * torch.from_numpy(wgt)).sum().backward()
+    want = {'y': ty.detach().numpy(), 'mean': x.mean(0), 'var': x.var(0),
+            'dx': tx.grad.numpy(), 'dscale': ts.grad.numpy(),
+            'doffset': to.grad.numpy()}
+    if with_side:
+        want['dside'] = tsd.grad.numpy()
+    return got, want
+
+
+def _check_bn_bf16(got, want):
+    for k in sorted(want):
+        print(k, 'max abs err', np.abs(got[k] - want[k]).max())
+    assert np.abs(got['y'] - want['y']).max() < 0.15
+    np.testing.assert_allclose(got['mean'], want['mean'], rtol=1e-2,
+                               atol=1e-2)
+    np.testing.assert_allclose(got['var'], want['var'], rtol=1e-2, atol=1e-2)
+    for k in sorted(set(want) - {'y', 'mean', 'var'}):
+        _grad_close_bf16(got[k], want[k])
+
+
+def _check_bn_f32(got, want):
+    for k in sorted(want):
+        print(k, 'max abs err', np.abs(got[k] - want[k]).max())
+    for k in sorted(want):
+        np.testing.assert_allclose(got[k], want[k], rtol=1e-4, atol=1e-4,
+                                   err_msg=k)
+
+
+def test_bn_bf16_fuse_relu_odd_rows_vs_torch():
+    # V9 kernels; 37 rows leave inactive threads in the last block
+    _check_bn_bf16(*_bn_case(tf.bfloat16, 37, 16, True, seed=20))
+
+
+def test_bn_add_relu_bf16_vs_torch():
+    _check_bn_bf16(*_bn_case(tf.bfloat16, 37, 16, True, seed=21,
+                             with_side=True))
+
+
+@pytest.mark.parametrize('fuse_relu', [False, True])
+def test_bn_bf16_scalar_path_vs_torch(fuse_relu):
+    # C % 8 != 0 takes the scalar kernels
+    _check_bn_bf16(*_bn_case(tf.bfloat16, 37, 12, fuse_relu, seed=22))
+
+
+@pytest.mark.parametrize('fuse_relu', [False, True])
+def test_bn_f32_c12_vs_torch(fuse_relu):
+    _check_bn_f32(*_bn_case(tf.float32, 37, 12, fuse_relu, seed=23))
+
+
+@pytest.mark.parametrize('fuse_relu', [False, True])
+def test_bn_f32_c16_vs_torch(fuse_relu):
+    # f32 with C % 8 == 0 must not take the 8-wide bf16 kernels
+    _check_bn_f32(*_bn_case(tf.float32, 37, 16, fuse_relu, seed=24))
+
+
+@pytest.mark.parametrize('fuse_relu', [False, True])
+def test_bn_bf16_multi_row_loop_vs_torch(fuse_relu):
+    # smallest row count with fewer row chunks (65536 at C=16) than rows:
+    # some threads of the V9 kernels take two rows, the rest one
+    _check_bn_bf16(*_bn_case(tf.bfloat16, 70001, 16, fuse_relu, seed=25))
+
+
+def _pool_planes(C, seed):
+    """x (2, 9, 9, C): every (n, c) plane is a permutation of 0..80 (exact
+    in bf16, unique maximum in every window); dy small integers so sums of
+    overlapping windows stay exact in bf16."""
+    rng = np.random.RandomState(seed)
+    x = np.stack([np.stack([rng.permutation(81).reshape(9, 9)
+                            for _ in range(C)], axis=-1)
+                  for _ in range(2)]).astype(np.float32)
+    dy = rng.randint(-3, 4, (2, 5, 5, C)).astype(np.float32)
+    return x, dy
+
+
+@pytest.mark.parametrize('C', [8, 4])
+def test_max_pool_3x3s2_same_vs_torch(C):
+    # P = Q = 5, pad 1: clipped border windows and overlapping windows.
+    # C=8: direct 8-wide gradient kernel; C=4: scalar kernel + f32 scratch.
+    x, dy = _pool_planes(C, seed=26)
+    xt = tf.constant(x, dtype=tf.bfloat16)
+    y = tf.nn.max_pool(xt, [1, 3, 3, 1], [1, 2, 2, 1], 'SAME')
+    loss = tf.reduce_sum(tf.cast(y, tf.float32) * tf.constant(dy))
+    got_y, got_g = _run([y, tf.gradients(loss, [xt])[0]])
+    tx = torch.from_numpy(x).permute(0, 3, 1, 2).requires_grad_(True)
+    ty = torch.nn.functional.max_pool2d(tx, 3, 2, padding=1)
+    (ty * torch.from_numpy(dy).permute(0, 3, 1, 2)).sum().backward()
+    assert got_y.shape == (2, 5, 5, C)
+    np.testing.assert_allclose(got_y, ty.detach().permute(0, 2, 3, 1).numpy(),
+                               atol=1e-2)
+    np.testing.assert_allclose(got_g, tx.grad.permute(0, 2, 3, 1).numpy(),
+                               atol=1e-2)
+
+
+@pytest.mark.parametrize('dtype,C', [('bfloat16', 8), ('bfloat16', 4),
+                                     ('float32', 4)])
+def test_avg_pool_3x3s2_same_vs_torch(dtype, C):
+    bf16 = dtype == 'bfloat16'
+    rnd = _round_bf16 if bf16 else (lambda a: a)
+    rng = np.random.RandomState(27)
+    x = rnd(rng.randn(2, 9, 9, C).astype(np.float32))
+    dy = rnd(rng.randn(2, 5, 5, C).astype(np.float32))
+    xt = tf.constant(x, dtype=getattr(tf, dtype))
+    y = tf.nn.avg_pool(xt, [1, 3, 3, 1], [1, 2, 2, 1], 'SAME')
+    loss = tf.reduce_sum(tf.cast(y, tf.float32) * tf.constant(dy))
+    got_y, got_g = _run([y, tf.gradients(loss, [xt])[0]])
+    tx = torch.from_numpy(x).permute(0, 3, 1, 2).requires_grad_(True)
+    ty = torch.nn.functional.avg_pool2d(tx, 3, 2, padding=1,
+                                        count_include_pad=False)
+    (ty * torch.from_numpy(dy).permute(0, 3, 1, 2)).sum().backward()
+    want_y = ty.detach().permute(0, 2, 3, 1).numpy()
+    want_g = tx.grad.permute(0, 2, 3, 1).numpy()
+    if bf16:
+        assert np.abs(got_y - want_y).max() < 0.05
+        _grad_close_bf16(got_g, want_g, bound=0.1)
+    else:
+        np.testing.assert_allclose(got_y, want_y, rtol=1e-4, atol=1e-4)
+        np.testing.assert_allclose(got_g, want_g, rtol=1e-4, atol=1e-4)

@@ -7,12 +7,21 @@
 namespace stf {
 namespace {
 
+// Views t as [outer, mid, inner]: outer is the product of the dims before
+// `begin`, inner the product of the dims from `end` on.
+void OuterInner(const Tensor& t, int begin, int end, int64_t* outer,
+                int64_t* inner) {
+  *outer = *inner = 1;
+  for (int i = 0; i < begin; ++i) *outer *= t.dim_size(i);
+  for (int i = end; i < t.dims(); ++i) *inner *= t.dim_size(i);
+}
+
 // ---------------------------------------------------------------------------
 // reductions: Sum / Mean / Max (all-axes, trailing-axes, or leading-axes)
 // ---------------------------------------------------------------------------
 class GpuReduceOp : public OpKernel {
  public:
-  GpuReduceOp(OpKernelConstruction* c, int red, bool mean)
+  GpuReduceOp(OpKernelConstruction* c, StfReduce red, bool mean)
       : OpKernel(c), red_(red), mean_(mean) {
     c->GetAttr("keep_dims", &keep_dims_);
   }
@@ -58,8 +67,8 @@ class GpuReduceOp : public OpKernel {
     for (int i = first_red; i <= last_red && i >= 0; ++i)
       if (!reduce[i]) contiguous = 0;
     if (all_red) {
-      float init = red_ == 0 ? 0.f : (red_ == 1 ? -3.4e38f : 3.4e38f);
-      OP_HIP_OK(ctx, stf_fill_f32(f32_out.raw_data(), init, 1, 0, s));
+      OP_HIP_OK(ctx, stf_fill_f32(f32_out.raw_data(), StfReduceIdentity(red_),
+                                  1, 0, s));
       OP_HIP_OK(ctx, stf_full_reduce(dt, red_, x.raw_data(),
                                      f32_out.flat<float>(), x.NumElements(),
                                      s));
@@ -84,25 +93,29 @@ class GpuReduceOp : public OpKernel {
   }
 
  private:
-  int red_;
+  StfReduce red_;
   bool mean_;
   bool keep_dims_ = false;
 };
 class SumGpu : public GpuReduceOp {
  public:
-  explicit SumGpu(OpKernelConstruction* c) : GpuReduceOp(c, 0, false) {}
+  explicit SumGpu(OpKernelConstruction* c)
+      : GpuReduceOp(c, STF_REDUCE_SUM, false) {}
 };
 class MeanGpu : public GpuReduceOp {
  public:
-  explicit MeanGpu(OpKernelConstruction* c) : GpuReduceOp(c, 0, true) {}
+  explicit MeanGpu(OpKernelConstruction* c)
+      : GpuReduceOp(c, STF_REDUCE_SUM, true) {}
 };
 class MaxGpu : public GpuReduceOp {
  public:
-  explicit MaxGpu(OpKernelConstruction* c) : GpuReduceOp(c, 1, false) {}
+  explicit MaxGpu(OpKernelConstruction* c)
+      : GpuReduceOp(c, STF_REDUCE_MAX, false) {}
 };
 class MinGpu : public GpuReduceOp {
  public:
-  explicit MinGpu(OpKernelConstruction* c) : GpuReduceOp(c, 2, false) {}
+  explicit MinGpu(OpKernelConstruction* c)
+      : GpuReduceOp(c, STF_REDUCE_MIN, false) {}
 };
 #define REG_GPU_REDUCE(OP, CLS)                                                \
   REGISTER_KERNEL_BUILDER(Name(OP).Device(DEVICE_GPU).TypeConstraint<float>("T").HostMemory("reduction_indices"), CLS); \
@@ -123,6 +136,9 @@ class GpuTileOp : public OpKernel {
     const Tensor& x = ctx->input(0);
     auto mult = IntVector(ctx->input(1));
     int rank = x.dims();
+    OP_REQUIRES(ctx, rank <= kStfMaxPermuteRank,
+                errors::Unimplemented("GPU Tile: rank above ",
+                                      kStfMaxPermuteRank));
     TensorShape out_shape;
     std::vector<int64_t> strides(rank), dims(rank);
     int64_t s_acc = 1;
@@ -137,10 +153,10 @@ class GpuTileOp : public OpKernel {
       out_shape.AddDim(dims[i]);
     }
     Tensor* y = ctx->allocate_output(0, out_shape);
-    OP_HIP_OK(ctx, stf_bcast_copy((int)DataTypeSize(x.dtype()), x.raw_data(),
-                                  y->raw_data(), out_shape.num_elements(),
-                                  rank, dims.data(), strides.data(),
-                                  GPU_STREAM(ctx)));
+    // a permute whose source stride is 0 on the tiled dims: broadcast
+    OP_HIP_OK(ctx, stf_permute((int)DataTypeSize(x.dtype()), x.raw_data(),
+                               y->raw_data(), out_shape.num_elements(), rank,
+                               dims.data(), strides.data(), GPU_STREAM(ctx)));
   }
 };
 REGISTER_KERNEL_BUILDER(Name("Tile").Device(DEVICE_GPU).HostMemory("multiples"), GpuTileOp);
@@ -152,6 +168,9 @@ class GpuTransposeOp : public OpKernel {
     const Tensor& x = ctx->input(0);
     auto perm = IntVector(ctx->input(1));
     int rank = x.dims();
+    OP_REQUIRES(ctx, rank <= kStfMaxPermuteRank,
+                errors::Unimplemented("GPU Transpose: rank above ",
+                                      kStfMaxPermuteRank));
     TensorShape out_shape;
     std::vector<int64_t> in_strides(rank, 1), src_strides(rank), dims(rank);
     for (int i = rank - 2; i >= 0; --i)
@@ -251,10 +270,8 @@ class GpuConcatV2Op : public OpKernel {
     for (int k = 0; k < n; ++k) total += ctx->input(k).dim_size((int)axis);
     out_shape.set_dim((int)axis, total);
     Tensor* y = ctx->allocate_output(0, out_shape);
-    int64_t outer = 1, inner = 1;
-    for (int i = 0; i < axis; ++i) outer *= first.dim_size(i);
-    for (int i = (int)axis + 1; i < first.dims(); ++i)
-      inner *= first.dim_size(i);
+    int64_t outer, inner;
+    OuterInner(first, (int)axis, (int)axis + 1, &outer, &inner);
     hipStream_t s = GPU_STREAM(ctx);
     int es = (int)DataTypeSize(first.dtype());
     int64_t off = 0;
@@ -282,9 +299,8 @@ class GpuSplitOp : public OpKernel {
     int64_t part = in.dim_size((int)axis) / n;
     TensorShape out_shape = in.shape();
     out_shape.set_dim((int)axis, part);
-    int64_t outer = 1, inner = 1;
-    for (int i = 0; i < axis; ++i) outer *= in.dim_size(i);
-    for (int i = (int)axis + 1; i < in.dims(); ++i) inner *= in.dim_size(i);
+    int64_t outer, inner;
+    OuterInner(in, (int)axis, (int)axis + 1, &outer, &inner);
     hipStream_t s = GPU_STREAM(ctx);
     int es = (int)DataTypeSize(in.dtype());
     for (int k = 0; k < n; ++k) {
@@ -309,9 +325,8 @@ class GpuPackOp : public OpKernel {
     TensorShape out_shape = first.shape();
     out_shape.InsertDim(axis, n);
     Tensor* y = ctx->allocate_output(0, out_shape);
-    int64_t outer = 1, inner = 1;
-    for (int i = 0; i < axis; ++i) outer *= first.dim_size(i);
-    for (int i = axis; i < first.dims(); ++i) inner *= first.dim_size(i);
+    int64_t outer, inner;
+    OuterInner(first, axis, axis, &outer, &inner);
     hipStream_t s = GPU_STREAM(ctx);
     int es = (int)DataTypeSize(first.dtype());
     for (int k = 0; k < n; ++k) {
@@ -337,9 +352,8 @@ class GpuUnpackOp : public OpKernel {
     int n = num_outputs();
     TensorShape out_shape = in.shape();
     out_shape.RemoveDim(axis);
-    int64_t outer = 1, inner = 1;
-    for (int i = 0; i < axis; ++i) outer *= in.dim_size(i);
-    for (int i = axis + 1; i < in.dims(); ++i) inner *= in.dim_size(i);
+    int64_t outer, inner;
+    OuterInner(in, axis, axis + 1, &outer, &inner);
     hipStream_t s = GPU_STREAM(ctx);
     int es = (int)DataTypeSize(in.dtype());
     for (int k = 0; k < n; ++k) {
@@ -432,9 +446,8 @@ class GpuSliceOp : public OpKernel {
                                     s));
       return;
     }
-    int64_t outer = 1, inner = 1;
-    for (int i = 0; i < cut; ++i) outer *= in.dim_size(i);
-    for (int i = cut + 1; i < rank; ++i) inner *= in.dim_size(i);
+    int64_t outer, inner;
+    OuterInner(in, cut, cut + 1, &outer, &inner);
     OP_HIP_OK(ctx, stf_strided_copy((int)DataTypeSize(in.dtype()), 0,
                                     in.raw_data(), y->raw_data(), outer,
                                     size[cut], inner, in.dim_size(cut),

@@ -71,6 +71,20 @@ inline void DispatchBool(bool flag, F&& f) {
   if (flag) f(std::true_type{});
   else f(std::false_type{});
 }
+// Same tag style for kernels typed by storage width only (layout copies:
+// 2 -> uint16_t, 4 -> uint32_t, else uint64_t) and by index type (int32_t
+// when idx_i32, else int64_t).
+template <typename F>
+inline void DispatchElemSize(int elem_size, F&& f) {
+  if (elem_size == 2) f(TypeTag<uint16_t>{});
+  else if (elem_size == 4) f(TypeTag<uint32_t>{});
+  else f(TypeTag<uint64_t>{});
+}
+template <typename F>
+inline void DispatchIndex(bool idx_i32, F&& f) {
+  if (idx_i32) f(TypeTag<int32_t>{});
+  else f(TypeTag<int64_t>{});
+}
 
 #define HIP_LAUNCH_CHECK()                                      \
   do {                                                           \

@@ -27,6 +27,18 @@ struct StfPoolGeom {
   int N, H, W, C, kh, kw, sh, sw, ph, pw, P, Q;
 };
 
+// Largest rank stf_permute takes.
+constexpr int kStfMaxPermuteRank = 6;
+
+// Reduction kinds of stf_full_reduce / stf_row_reduce / stf_col_reduce, and
+// the value each kind starts from (stf_full_reduce expects out_f32 pre-filled
+// with it).
+enum StfReduce { STF_REDUCE_SUM = 0, STF_REDUCE_MAX = 1, STF_REDUCE_MIN = 2 };
+constexpr float StfReduceIdentity(StfReduce kind) {
+  return kind == STF_REDUCE_SUM ? 0.f
+         : kind == STF_REDUCE_MAX ? -3.4e38f : 3.4e38f;
+}
+
 extern "C" {
 
 // ---- gemm_bf16.hip / gemm_bf16_8ph.hip / gemm_f32.hip ----
@@ -178,26 +190,40 @@ hipError_t stf_lstm_gates_grad(int dtype, const void* c_prev, const void* i_,
                                void* dgates, void* dc_prev, int64_t batch,
                                int H, hipStream_t stream);
 
-// ---- transform.hip ----
+// ---- layout.hip ----
+// elem_size is 2, 4 or 8 bytes: these copy bits whatever the dtype.
 hipError_t stf_transpose2d(int elem_size, const void* in, void* out,
                            int64_t rows, int64_t cols, hipStream_t stream);
+// out[i] = in[sum_d coord_d(i) * src_strides[d]] over out_dims; a stride of 0
+// broadcasts that dim. hipErrorInvalidValue unless
+// 0 <= rank <= kStfMaxPermuteRank.
 hipError_t stf_permute(int elem_size, const void* in, void* out, int64_t n,
                        int rank, const int64_t* out_dims,
                        const int64_t* src_strides, hipStream_t stream);
-hipError_t stf_bcast_copy(int elem_size, const void* in, void* out, int64_t n,
-                          int rank, const int64_t* out_dims,
-                          const int64_t* src_strides, hipStream_t stream);
 hipError_t stf_block_pad(int dtype, const void* src, void* dst,
                          int64_t nblocks, int64_t in_block, int64_t out_block,
                          hipStream_t stream);
+// Moves [outer, rows, inner] between a contiguous side and rows
+// [row_off, row_off + rows) of a [outer, big_stride, inner] side; scatter:
+// contiguous src -> strided dst.
+hipError_t stf_strided_copy(int elem_size, int scatter, const void* src,
+                            void* dst, int64_t outer, int64_t rows,
+                            int64_t inner, int64_t big_stride,
+                            int64_t row_off, hipStream_t stream);
+
+// ---- reduce.hip ----
+// Accumulates 0.5 * sum(x^2) into a zeroed out_f32.
 hipError_t stf_l2loss(int dtype, const void* x, float* out_f32, int64_t n,
                       hipStream_t stream);
-hipError_t stf_full_reduce(int dtype, int red, const void* x, float* out_f32,
-                           int64_t n, hipStream_t stream);
-hipError_t stf_row_reduce(int dtype, int red, const void* x, float* y,
+hipError_t stf_full_reduce(int dtype, StfReduce red, const void* x,
+                           float* out_f32, int64_t n, hipStream_t stream);
+hipError_t stf_row_reduce(int dtype, StfReduce red, const void* x, float* y,
                           int64_t rows, int64_t inner, hipStream_t stream);
-hipError_t stf_col_reduce(int dtype, int red, const void* x, float* y,
+hipError_t stf_col_reduce(int dtype, StfReduce red, const void* x, float* y,
                           int64_t outer, int64_t inner, hipStream_t stream);
+
+// ---- optimizer.hip ----
+// f32 variables and slots; hyper-parameters are device f32 scalars.
 hipError_t stf_apply_sgd(int grad_bf16, void* var, const void* lr,
                          const void* grad, int64_t n, hipStream_t stream);
 hipError_t stf_apply_momentum(int grad_bf16, void* var, void* accum,
@@ -208,21 +234,23 @@ hipError_t stf_apply_adam(int grad_bf16, void* var, void* m, void* v,
                           const void* b1p, const void* b2p, const void* lr,
                           const void* b1, const void* b2, const void* eps,
                           const void* grad, int64_t n, hipStream_t stream);
-hipError_t stf_strided_copy(int elem_size, int scatter, const void* src,
-                            void* dst, int64_t outer, int64_t rows,
-                            int64_t inner, int64_t big_stride,
-                            int64_t row_off, hipStream_t stream);
-hipError_t stf_gather_rows(int dtype, int idx_i32, const void* params,
-                           const void* indices, void* out, int64_t nidx,
-                           int64_t row, int64_t nrows, hipStream_t stream);
-hipError_t stf_segment_sum(int dtype, int idx_i32, const void* data,
-                           const void* ids, float* out_f32, int64_t nidx,
-                           int64_t row, int64_t nseg, hipStream_t stream);
+
+// ---- random.hip ----
+// ctr_dev: device uint64 Philox offset, advanced by each call.
 hipError_t stf_random_uniform(uint64_t seed, void* ctr_dev, void* out,
                               int64_t n, int as_bf16, hipStream_t stream);
 hipError_t stf_random_normal(uint64_t seed, void* ctr_dev, void* out,
                              int64_t n, int as_bf16, int truncated,
                              hipStream_t stream);
+
+// ---- embedding.hip ----
+hipError_t stf_gather_rows(int dtype, int idx_i32, const void* params,
+                           const void* indices, void* out, int64_t nidx,
+                           int64_t row, int64_t nrows, hipStream_t stream);
+// out_f32 must be zeroed.
+hipError_t stf_segment_sum(int dtype, int idx_i32, const void* data,
+                           const void* ids, float* out_f32, int64_t nidx,
+                           int64_t row, int64_t nseg, hipStream_t stream);
 
 // ---- comm_pack.hip ----
 int stf_comm_max_segments();

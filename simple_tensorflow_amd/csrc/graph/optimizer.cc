@@ -423,13 +423,12 @@ int FuseElementwise(Graph* g, const std::set<std::string>& preserve) {
     }
     fused_total += (int)chain.size();
     }  // exits
-    // drop members that nothing external consumes anymore (reverse topo)
-    for (auto it = members.rbegin(); it != members.rend(); ++it) {
-      bool busy = false;
-      for (const Edge* e : (*it)->out_edges)
-        if (!mem.count(e->dst)) busy = true;
-      if (!busy) g->RemoveNode(*it);
-    }
+    // drop members that nothing consumes anymore (reverse topo, so a removed
+    // consumer has already released its producers). An exit that was not
+    // fused (program or input limit) keeps its consumers, and with them its
+    // whole closure.
+    for (auto it = members.rbegin(); it != members.rend(); ++it)
+      if ((*it)->out_edges.empty()) g->RemoveNode(*it);
   }
   return fused_total;
 }

@@ -64,13 +64,15 @@ class GpuBinaryOp : public OpKernel {
                                 y->raw_data(), a.NumElements(), s));
       return;
     }
-    if (b.NumElements() == 1) {
+    // Scalar paths: the output takes the other side's shape, which is the
+    // broadcast shape only while the scalar's rank does not exceed it.
+    if (b.NumElements() == 1 && b.dims() <= a.dims()) {
       Tensor* y = ctx->allocate_output(0, a.shape());
       OP_HIP_OK(ctx, stf_binary_scalar(op_, dt, a.raw_data(), b.raw_data(),
                                        y->raw_data(), a.NumElements(), 0, s));
       return;
     }
-    if (a.NumElements() == 1) {
+    if (a.NumElements() == 1 && a.dims() <= b.dims()) {
       Tensor* y = ctx->allocate_output(0, b.shape());
       OP_HIP_OK(ctx, stf_binary_scalar(op_, dt, b.raw_data(), a.raw_data(),
                                        y->raw_data(), b.NumElements(), 1, s));

@@ -28,7 +28,10 @@ __device__ __forceinline__ float UEval(UOp op, float a) {
     case UOp::SIGMOID: return 1.f / (1.f + __expf(-a));
     case UOp::RELU: return a > 0.f ? a : 0.f;
     case UOp::RELU6: return a < 0.f ? 0.f : (a > 6.f ? 6.f : a);
-    case UOp::SOFTPLUS: return log1pf(__expf(a));
+    // stable for large |a| (exp(a) overflows above ~88.7); same form as the
+    // fused interpreter's opcode 13
+    case UOp::SOFTPLUS:
+      return log1pf(__expf(-fabsf(a))) + (a > 0.f ? a : 0.f);
     case UOp::RECIP: return 1.f / a;
     case UOp::FLOOR: return floorf(a);
     case UOp::CEIL: return ceilf(a);
@@ -149,19 +152,26 @@ __global__ void BinaryBcastKernel(BOp op, const T* __restrict__ a,
 }
 
 // ---- cast ----
+// Converts directly, so integer pairs keep every bit; only a __bf16 side
+// goes through float.
+template <typename S, typename D>
+__device__ __forceinline__ D CastOne(S v) {
+  if constexpr (std::is_same<D, bool>::value) {
+    return v != S(0);
+  } else if constexpr (std::is_same<S, __bf16>::value ||
+                       std::is_same<D, __bf16>::value) {
+    return (D)(float)v;
+  } else {
+    return (D)v;
+  }
+}
+
 template <typename S, typename D>
 __global__ void CastKernel(const S* __restrict__ x, D* __restrict__ y,
                            int64_t n) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    y[i] = (D)(float)x[i];
-}
-template <>
-__global__ void CastKernel<float, int32_t>(const float* __restrict__ x,
-                                           int32_t* __restrict__ y, int64_t n) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    y[i] = (int32_t)x[i];
+    y[i] = CastOne<S, D>(x[i]);
 }
 
 // ---- scale by immediate ----
@@ -382,7 +392,8 @@ extern "C" hipError_t stf_binary_bcast(int op, int dtype, const void* a,
   return hipGetLastError();
 }
 
-// src/dst dtype codes: 0 f32, 1 bf16, 2 f16, 3 i32, 4 i64, 5 bool
+// src/dst dtype codes: 0 f32, 1 bf16, 2 f16 (no kernel), 3 i32, 4 i64,
+// 5 bool; an unlisted pair returns hipErrorInvalidValue
 extern "C" hipError_t stf_cast(int sdt, int ddt, const void* x, void* y,
                                int64_t n, hipStream_t stream) {
   dim3 grid = ElemwiseGrid(n, 256, 4);

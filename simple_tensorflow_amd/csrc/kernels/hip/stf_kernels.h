@@ -5,7 +5,9 @@
 // of silently corrupted arguments at run time.
 //
 // Conventions: dtype codes are 0 = f32, 1 = bf16 (stf_cast: 0 f32, 1 bf16,
-// 2 f16, 3 i32, 4 i64, 5 bool); all launches are asynchronous on `stream`.
+// 2 f16, 3 i32, 4 i64, 5 bool; no f16 kernel exists, so a pair with code 2,
+// like any pair it does not list, returns hipErrorInvalidValue); all launches
+// are asynchronous on `stream`.
 #pragma once
 
 #include <hip/hip_runtime_api.h>

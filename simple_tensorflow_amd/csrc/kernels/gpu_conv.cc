@@ -189,6 +189,9 @@ class GpuConv2DBackpropInputOp : public OpKernel {
       : OpKernel(c), side_(side) {
     c->GetAttr("strides", &strides_);
     c->GetAttr("padding", &padding_);
+    // STF_NO_IMPLICIT_DX (A/B runs) sends every dx back through GEMM +
+    // col2im. Read per kernel, so a new graph sees a changed setting.
+    implicit_dx_ = getenv("STF_NO_IMPLICIT_DX") == nullptr;
   }
   void Compute(OpKernelContext* ctx) override {
     auto in_sizes = IntVector(ctx->input(0));
@@ -217,6 +220,25 @@ class GpuConv2DBackpropInputOp : public OpKernel {
                                             g.RSC(), g.K, g.K, g.K, s));
       return;
     }
+    // Stride 1: dx is itself a stride-1 convolution of dy with the flipped,
+    // channel-swapped filter, so it runs on the implicit-GEMM 8-phase kernel
+    // and the R*S-times-wider dcol is never written or read back. Shapes
+    // outside the 8-phase gate keep GEMM + col2im: through the general NT
+    // template the implicit dx measured 3% slower end to end on Inception v3.
+    StfConvGeom sg = g.abi();
+    int64_t nhw = g.N * g.H * g.W;
+    int64_t rskp = (g.R * g.S * g.K + 63) & ~int64_t(63);
+    bool implicit = implicit_dx_ && g.sh == 1 && g.sw == 1 &&
+                    !g.is_1x1_s1() && (g.K % 8) == 0 && ZeroPage();
+    if (implicit && stf_gemm_bf16_8ph_ok(nhw, g.C, rskp)) {
+      Tensor wt = ctx->allocate_temp(DT_BFLOAT16, TensorShape({g.C, rskp}));
+      OP_HIP_OK(ctx, stf_conv_dx_filter(w.raw_data(), wt.raw_data(), (int)g.R,
+                                        (int)g.S, (int)g.C, g.K, rskp, s));
+      OP_HIP_OK(ctx, stf_conv2d_dx_8ph(dy.raw_data(), wt.raw_data(),
+                                       dx->raw_data(), side, ZeroPage(), &sg,
+                                       rskp, s));
+      return;
+    }
     if (g.is_1x1_s1()) {
       OP_HIP_OK(ctx, stf_gemm_bf16_nt(dy.raw_data(), w.raw_data(),
                                       dx->raw_data(), g.M(), g.RSC(), g.K, s));
@@ -226,10 +248,12 @@ class GpuConv2DBackpropInputOp : public OpKernel {
       OP_HIP_OK(ctx, stf_gemm_bf16_nt(dy.raw_data(), w.raw_data(),
                                       dcol.raw_data(), g.M(), g.RSC(), g.K,
                                       s));
-      StfConvGeom sg = g.abi();
-      OP_HIP_OK(ctx, stf_col2im_bf16(dcol.raw_data(), dx->raw_data(), &sg, s));
+      // col2im writes every dx element once and takes side in that store
+      OP_HIP_OK(ctx, stf_col2im_bf16(dcol.raw_data(), side, dx->raw_data(),
+                                     &sg, s));
+      return;
     }
-    if (side)
+    if (side)  // 1x1/s1 outside the 8-phase gate
       OP_HIP_OK(ctx, stf_binary(B_ADD, DtypeCode(DT_BFLOAT16), dx->raw_data(),
                                 side, dx->raw_data(), dx->NumElements(), s));
   }
@@ -238,6 +262,7 @@ class GpuConv2DBackpropInputOp : public OpKernel {
   std::vector<int64_t> strides_;
   std::string padding_;
   bool side_;
+  bool implicit_dx_;
 };
 REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropInput").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("input_sizes"), GpuConv2DBackpropInputOp);
 

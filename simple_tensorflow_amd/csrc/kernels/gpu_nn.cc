@@ -218,8 +218,8 @@ class GpuBatchNormMiGradOp : public OpKernel {
                               x.raw_data(), y_relu.raw_data(),
                               mean.flat<float>(), inv_std.flat<float>(),
                               scale.raw_data(), doffset->flat<float>(),
-                              dscale->flat<float>(), dx->raw_data(), rows, c,
-                              fuse_relu_ ? 1 : 0, s));
+                              dscale->flat<float>(), dx->raw_data(), nullptr,
+                              rows, c, fuse_relu_ ? 1 : 0, s));
   }
 
  private:
@@ -244,16 +244,13 @@ class GpuBatchNormAddReluMiGradOp : public OpKernel {
     hipStream_t s = GPU_STREAM(ctx);
     OP_HIP_OK(ctx, ZeroF32(doffset->raw_data(), c, s));
     OP_HIP_OK(ctx, ZeroF32(dscale->raw_data(), c, s));
+    // dside (the ReLU-masked dy) is stored by the same kernel that writes dx
     OP_HIP_OK(ctx, stf_bn_bwd(DtypeCode(x.dtype()), dy.raw_data(),
                               x.raw_data(), y_relu.raw_data(),
                               mean.flat<float>(), inv_std.flat<float>(),
                               scale.raw_data(), doffset->flat<float>(),
-                              dscale->flat<float>(), dx->raw_data(), rows, c,
-                              1, s));
-    // dside = relu-masked dy
-    OP_HIP_OK(ctx, stf_binary(B_RELU_GRAD, DtypeCode(x.dtype()),
-                              dy.raw_data(), y_relu.raw_data(),
-                              dside->raw_data(), x.NumElements(), s));
+                              dscale->flat<float>(), dx->raw_data(),
+                              dside->raw_data(), rows, c, 1, s));
   }
 };
 REGISTER_KERNEL_BUILDER(Name("BatchNormAddReluMiGrad").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuBatchNormAddReluMiGradOp);

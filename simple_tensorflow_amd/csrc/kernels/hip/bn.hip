@@ -113,7 +113,10 @@ __global__ void BnGradStatsKernel(const T* __restrict__ dy,
 }
 
 // bwd pass 2: dx = scale*inv_std*(dy - sum_dy/rows - xhat*sum_dy_xhat/rows)
-template <typename T, bool RELU>
+// DSIDE (with RELU, the BN+add+ReLU tail): dy and yr are in registers here, so
+// the residual branch's gradient dside = yr > 0 ? dy : 0 is one more store
+// instead of a separate pass. A NaN in yr gives 0, as the relu-grad op does.
+template <typename T, bool RELU, bool DSIDE>
 __global__ void BnGradKernel(const T* __restrict__ dy, const T* __restrict__ x,
                              const T* __restrict__ yr,
                              const float* __restrict__ mean,
@@ -121,8 +124,8 @@ __global__ void BnGradKernel(const T* __restrict__ dy, const T* __restrict__ x,
                              const float* __restrict__ scale,
                              const float* __restrict__ sum_dy,
                              const float* __restrict__ sum_dy_xhat,
-                             T* __restrict__ dx, int64_t n, int64_t rows,
-                             int c) {
+                             T* __restrict__ dx, T* __restrict__ dside,
+                             int64_t n, int64_t rows, int c) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   float inv_rows = 1.f / (float)rows;
   for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -133,6 +136,7 @@ __global__ void BnGradKernel(const T* __restrict__ dy, const T* __restrict__ x,
     dx[i] = (T)(scale[ch] * inv_std[ch] *
                 (g - sum_dy[ch] * inv_rows -
                  xhat * sum_dy_xhat[ch] * inv_rows));
+    if (DSIDE) dside[i] = (T)((float)yr[i] > 0.f ? (float)dy[i] : 0.f);
   }
 }
 
@@ -341,7 +345,7 @@ __global__ void BnGradStatsKernelV9(const __bf16* __restrict__ dy,
     }
 }
 
-template <bool RELU>
+template <bool RELU, bool DSIDE>
 __global__ void BnGradKernelV9(const __bf16* __restrict__ dy,
                                const __bf16* __restrict__ x,
                                const __bf16* __restrict__ yr,
@@ -350,7 +354,9 @@ __global__ void BnGradKernelV9(const __bf16* __restrict__ dy,
                                const float* __restrict__ scale,
                                const float* __restrict__ sum_dy,
                                const float* __restrict__ sum_dy_xhat,
-                               __bf16* __restrict__ dx, int64_t rows, int c) {
+                               __bf16* __restrict__ dx,
+                               __bf16* __restrict__ dside, int64_t rows,
+                               int c) {
   BnIdx ix = BnThreadIndex(c, rows);
   if (!ix.active) return;
   int cb = ix.w * 8;
@@ -365,7 +371,7 @@ __global__ void BnGradKernelV9(const __bf16* __restrict__ dy,
     b[e] = sum_dy_xhat[cb + e] * inv_rows;
   }
   for (int64_t r = ix.chunk; r < rows; r += ix.chunks) {
-    __bf16 g8[8], x8[8], y8[8], o[8];
+    __bf16 g8[8], x8[8], y8[8], o[8], ds[8];
     Load8(g8, dy + r * c + cb);
     Load8(x8, x + r * c + cb);
     if (RELU) Load8(y8, yr + r * c + cb);
@@ -375,8 +381,10 @@ __global__ void BnGradKernelV9(const __bf16* __restrict__ dy,
       float g = (float)g8[e];
       if (RELU && (float)y8[e] <= 0.f) g = 0.f;
       o[e] = (__bf16)(k[e] * (g - a[e] - xhat * b[e]));
+      if (DSIDE) ds[e] = (__bf16)((float)y8[e] > 0.f ? (float)g8[e] : 0.f);
     }
     Store8(dx + r * c + cb, o);
+    if (DSIDE) Store8(dside + r * c + cb, ds);
   }
 }
 
@@ -459,8 +467,9 @@ hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
                       const void* y_relu, const float* mean,
                       const float* inv_std, const void* scale,
                       float* sum_dy, float* sum_dy_xhat, void* dx,
-                      int64_t rows, int c, int fuse_relu,
+                      void* dside, int64_t rows, int c, int fuse_relu,
                       hipStream_t stream) {
+  if (dside && !fuse_relu) return hipErrorInvalidValue;
   DispatchBool(fuse_relu, [&](auto relu) {
     constexpr bool RELU = decltype(relu)::value;
     if (UseV9(dtype, c)) {
@@ -469,11 +478,14 @@ hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
                          BnLdsBytes(c), stream, (const __bf16*)dy,
                          (const __bf16*)x, (const __bf16*)y_relu, mean,
                          inv_std, sum_dy, sum_dy_xhat, rows, c);
-      hipLaunchKernelGGL((BnGradKernelV9<RELU>), g9, dim3(256), 0, stream,
-                         (const __bf16*)dy, (const __bf16*)x,
-                         (const __bf16*)y_relu, mean, inv_std,
-                         (const float*)scale, sum_dy, sum_dy_xhat,
-                         (__bf16*)dx, rows, c);
+      DispatchBool(RELU && dside, [&](auto ds) {
+        constexpr bool DSIDE = RELU && decltype(ds)::value;
+        hipLaunchKernelGGL((BnGradKernelV9<RELU, DSIDE>), g9, dim3(256), 0,
+                           stream, (const __bf16*)dy, (const __bf16*)x,
+                           (const __bf16*)y_relu, mean, inv_std,
+                           (const float*)scale, sum_dy, sum_dy_xhat,
+                           (__bf16*)dx, (__bf16*)dside, rows, c);
+      });
       return;
     }
     DispatchDtype(dtype, [&](auto t) {
@@ -483,11 +495,14 @@ hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
                          BnLdsBytes(c), stream, (const T*)dy, (const T*)x,
                          (const T*)y_relu, mean, inv_std, sum_dy, sum_dy_xhat,
                          rows, c);
-      hipLaunchKernelGGL((BnGradKernel<T, RELU>), ElemwiseGrid(n, 256, 4),
-                         dim3(256), 0, stream, (const T*)dy, (const T*)x,
-                         (const T*)y_relu, mean, inv_std,
-                         (const float*)scale, sum_dy, sum_dy_xhat, (T*)dx, n,
-                         rows, c);
+      DispatchBool(RELU && dside, [&](auto ds) {
+        constexpr bool DSIDE = RELU && decltype(ds)::value;
+        hipLaunchKernelGGL((BnGradKernel<T, RELU, DSIDE>),
+                           ElemwiseGrid(n, 256, 4), dim3(256), 0, stream,
+                           (const T*)dy, (const T*)x, (const T*)y_relu, mean,
+                           inv_std, (const float*)scale, sum_dy, sum_dy_xhat,
+                           (T*)dx, (T*)dside, n, rows, c);
+      });
     });
   });
   return hipGetLastError();

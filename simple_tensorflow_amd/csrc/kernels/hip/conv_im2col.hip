@@ -50,8 +50,11 @@ __global__ void Im2ColKernel(const __bf16* __restrict__ x,
 }
 
 // gather-form col2im (deterministic, no atomics): each dX element sums its
-// contributors from dcol.
+// contributors from dcol. Every dX element is written once by one thread, so
+// an optional `side` (residual gradient) is added in the store: the sum is
+// rounded to bf16 first, exactly as a separate add pass over dX would see it.
 __global__ void Col2ImKernel(const __bf16* __restrict__ dcol,
+                             const __bf16* __restrict__ side,
                              __bf16* __restrict__ dx, ConvGeom g,
                              int64_t total) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -78,7 +81,9 @@ __global__ void Col2ImKernel(const __bf16* __restrict__ dcol,
         acc += (float)dcol[m * RSC + (int64_t)(r * g.S + s) * g.C + c];
       }
     }
-    dx[i] = (__bf16)acc;
+    __bf16 o = (__bf16)acc;
+    if (side) o = (__bf16)((float)o + (float)side[i]);
+    dx[i] = o;
   }
 }
 
@@ -86,6 +91,7 @@ __global__ void Col2ImKernel(const __bf16* __restrict__ dcol,
 // vector loads per filter tap and a single 16B store (col2im is pure
 // HBM-bound gather; vectorization is the whole game).
 __global__ void Col2ImKernelV8(const __bf16* __restrict__ dcol,
+                               const __bf16* __restrict__ side,
                                __bf16* __restrict__ dx, ConvGeom g,
                                int64_t total8) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -120,7 +126,43 @@ __global__ void Col2ImKernelV8(const __bf16* __restrict__ dcol,
     __bf16 out[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) out[e] = (__bf16)acc[e];
+    if (side) {
+      __bf16 sv[8];
+      *(ulong2*)sv = *(const ulong2*)(side + i * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        out[e] = (__bf16)((float)out[e] + (float)sv[e]);
+    }
     *(ulong2*)(dx + i * 8) = *(ulong2*)out;
+  }
+}
+
+// Filter operand of the implicit-GEMM backward-input: dx is a stride-1
+// convolution of dy with the filter flipped spatially and its channel axes
+// swapped. From w[R,S,C,K] this writes, for j = (r'*S + s')*K + k,
+//   out(c, j) = w[R-1-r'][S-1-s'][c][k],  j < R*S*K;   0 for j in [RSK, rscp)
+// contraction-innermost, out[c*rscp + j]: the 8-phase kernel's NT operand.
+// For a fixed (r, s) the source is already a row-major [C, K] block, so this
+// is a block-permuting copy. K % 8 == 0: one thread moves 8 consecutive k.
+__global__ void ConvDxFilterKernel(const __bf16* __restrict__ w,
+                                   __bf16* __restrict__ out, int R, int S,
+                                   int C, int K, int64_t rscp,
+                                   int64_t total8) {
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t j8n = rscp / 8, rsk = (int64_t)R * S * K;
+  for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total8;
+       i += stride) {
+    int c = (int)(i / j8n);
+    int64_t j = (i % j8n) * 8;
+    __bf16 v[8];
+    *(ulong2*)v = ulong2{0, 0};
+    if (j < rsk) {
+      int rs = (int)(j / K), k = (int)(j % K);
+      int r = R - 1 - rs / S, s_ = S - 1 - rs % S;
+      *(ulong2*)v =
+          *(const ulong2*)(w + ((int64_t)(r * S + s_) * C + c) * K + k);
+    }
+    *(ulong2*)(out + c * rscp + j) = *(ulong2*)v;
   }
 }
 
@@ -145,8 +187,8 @@ extern "C" hipError_t stf_im2col_bf16(const void* x, void* col,
   return hipGetLastError();
 }
 
-extern "C" hipError_t stf_col2im_bf16(const void* dcol, void* dx,
-                                      const StfConvGeom* sg,
+extern "C" hipError_t stf_col2im_bf16(const void* dcol, const void* side,
+                                      void* dx, const StfConvGeom* sg,
                                       hipStream_t stream) {
   ConvGeom g = DeviceGeom(*sg);
   int64_t total = (int64_t)g.N * g.H * g.W * g.C;
@@ -154,10 +196,23 @@ extern "C" hipError_t stf_col2im_bf16(const void* dcol, void* dx,
     int64_t total8 = total / 8;
     hipLaunchKernelGGL(Col2ImKernelV8, ElemwiseGrid(total8, 256, 1),
                        dim3(256), 0, stream, (const __bf16*)dcol,
-                       (__bf16*)dx, g, total8);
+                       (const __bf16*)side, (__bf16*)dx, g, total8);
   } else {
     hipLaunchKernelGGL(Col2ImKernel, ElemwiseGrid(total, 256, 1), dim3(256),
-                       0, stream, (const __bf16*)dcol, (__bf16*)dx, g, total);
+                       0, stream, (const __bf16*)dcol, (const __bf16*)side,
+                       (__bf16*)dx, g, total);
   }
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_conv_dx_filter(const void* w, void* out, int r,
+                                         int s, int c, int64_t k,
+                                         int64_t rscp, hipStream_t stream) {
+  if (k % 8 != 0 || rscp % 8 != 0 || rscp < (int64_t)r * s * k)
+    return hipErrorInvalidValue;
+  int64_t total8 = (int64_t)c * (rscp / 8);
+  hipLaunchKernelGGL(ConvDxFilterKernel, ElemwiseGrid(total8, 256, 1),
+                     dim3(256), 0, stream, (const __bf16*)w, (__bf16*)out, r,
+                     s, c, (int)k, rscp, total8);
   return hipGetLastError();
 }

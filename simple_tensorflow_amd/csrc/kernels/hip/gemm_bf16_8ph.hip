@@ -331,4 +331,21 @@ hipError_t stf_conv2d_fwd_8ph(const void* x, const void* wt, void* y,
                    rscp, rscp, stream);
 }
 
+// Implicit-GEMM Conv2D backward-input for stride 1: dx[M=NHW, C] =
+// im2col(dy) * wt[C, rscp]^T over the swapped geometry (ConvDxGeom), wt the
+// flipped filter from stf_conv_dx_filter. Same kernel as the forward conv;
+// `side` (residual gradient) goes through its epilogue.
+hipError_t stf_conv2d_dx_8ph(const void* dy, const void* wt, void* dx,
+                             const void* side, const void* zero16,
+                             const StfConvGeom* g, int64_t rscp,
+                             hipStream_t stream) {
+  int64_t M = (int64_t)g->n * g->h * g->w;
+  if (g->sh != 1 || g->sw != 1 || (g->cout % 8) != 0 ||
+      !stf_gemm_bf16_8ph_ok(M, g->c, rscp) ||
+      rscp < (int64_t)g->r * g->s * g->cout)
+    return hipErrorInvalidValue;
+  return Launch8Ph(MakeConvAG(ConvDxGeom(*g), dy, zero16), wt, dx, side, M,
+                   g->c, rscp, rscp, stream);
+}
+
 }  // extern "C"

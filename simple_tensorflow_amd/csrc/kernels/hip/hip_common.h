@@ -175,3 +175,14 @@ inline ConvAG MakeConvAG(const StfConvGeom& g, const void* x,
   ag.rsc = (int64_t)g.r * g.s * g.c;
   return ag;
 }
+
+// Geometry of the convolution that computes the backward-input of the
+// stride-1 forward convolution g: its input is dy [n,p,q,cout], its output
+// dx [n,h,w,c], and the padding is what is left of the filter on the other
+// side (dx[h] takes dy[h + ph - r], i.e. filter row r' = R-1-r at offset
+// h - (R-1-ph) + r'). ConvAG::at bounds-checks both edges, so VALID padding
+// and even or non-square filters need nothing more.
+inline StfConvGeom ConvDxGeom(const StfConvGeom& g) {
+  return StfConvGeom{g.n, g.p, g.q, (int)g.cout, g.r, g.s, /*sh=*/1, /*sw=*/1,
+                     g.r - 1 - g.ph, g.s - 1 - g.pw, g.h, g.w, (int64_t)g.c};
+}

@@ -81,8 +81,23 @@ hipError_t stf_conv2d_dw_splitk(const void* x, const void* dy, void* dw_f32,
                                 int splitk, hipStream_t stream);
 hipError_t stf_im2col_bf16(const void* x, void* col, const StfConvGeom* g,
                            int64_t ld, hipStream_t stream);
-hipError_t stf_col2im_bf16(const void* dcol, void* dx, const StfConvGeom* g,
-                           hipStream_t stream);
+// dx = col2im(dcol) (+ side, optional [n,h,w,c] bf16, added after the sum is
+// rounded to bf16).
+hipError_t stf_col2im_bf16(const void* dcol, const void* side, void* dx,
+                           const StfConvGeom* g, hipStream_t stream);
+// Implicit-GEMM backward-input of a stride-1 conv: dx[NHW, C] = conv(dy,
+// flipped filter), no column buffer. g is the forward geometry; k = cout must
+// be a multiple of 8. The filter operand comes from stf_conv_dx_filter:
+// w[r,s,c,k] -> wt[c][(r'*s + s')*k + kk] = w[r-1-r'][s-1-s'][c][kk], zero
+// for columns in [r*s*k, rscp). rscp = r*s*k rounded up to 64.
+hipError_t stf_conv_dx_filter(const void* w, void* wt, int r, int s, int c,
+                              int64_t k, int64_t rscp, hipStream_t stream);
+// side: optional [NHW, C] bf16 added in the epilogue. Needs
+// stf_gemm_bf16_8ph_ok(NHW, c, rscp).
+hipError_t stf_conv2d_dx_8ph(const void* dy, const void* wt, void* dx,
+                             const void* side, const void* zero16,
+                             const StfConvGeom* g, int64_t rscp,
+                             hipStream_t stream);
 
 // ---- depthwise.hip ----
 // Filter is [r, s, c, mult]; g->cout is unused.
@@ -159,12 +174,13 @@ hipError_t stf_bn_add_relu(const void* x, const void* side, const float* mean,
                            const void* offset, void* y, int64_t rows, int c,
                            hipStream_t stream);
 // sum_dy (= doffset) and sum_dy_xhat (= dscale) are zeroed f32 [c] and are
-// accumulated in place.
+// accumulated in place. dside (optional, fuse_relu only): also receives the
+// ReLU-masked dy, y_relu > 0 ? dy : 0, the gradient of the residual branch.
 hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
                       const void* y_relu, const float* mean,
                       const float* inv_std, const void* scale, float* sum_dy,
-                      float* sum_dy_xhat, void* dx, int64_t rows, int c,
-                      int fuse_relu, hipStream_t stream);
+                      float* sum_dy_xhat, void* dx, void* dside, int64_t rows,
+                      int c, int fuse_relu, hipStream_t stream);
 
 // ---- pool.hip ----
 hipError_t stf_pool_fwd(int dtype, int is_max, const void* x, void* y,

@@ -55,8 +55,6 @@ DirectSession::DirectSession(bool force_cpu_only, int num_threads) {
   resource_mgr_ = NewResourceMgr();
 }
 
-DirectSession::~DirectSession() { DeleteResourceMgr(resource_mgr_); }
-
 Status DirectSession::Create(const GraphDef& def) {
   std::lock_guard<std::mutex> l(mu_);
   graph_def_ = def;
@@ -611,6 +609,29 @@ Status DirectSession::PartialRun(
     partial_runs_.erase(handle);
   }
   return fetch_status;
+}
+
+// A partial run that was set up but never finished (a PartialRun call that
+// failed validation returns before the tear-down above) still has executors
+// in flight: queued on the pool or parked on the step rendezvous. They use
+// the executors, devices and resource manager this object owns, so abort
+// them and wait for them before anything is destroyed.
+DirectSession::~DirectSession() {
+  std::map<std::string, std::shared_ptr<PartialRunState>> pending;
+  {
+    std::lock_guard<std::mutex> l(mu_);
+    pending.swap(partial_runs_);
+  }
+  for (auto& kv : pending) {
+    PartialRunState& prs = *kv.second;
+    prs.rendez->StartAbort(errors::Cancelled("session closed"));
+    std::unique_lock<std::mutex> l(prs.mu);
+    // bounded: a kernel parked outside the rendezvous (a queue waiter) is
+    // never resumed once the resource manager is gone
+    prs.cv.wait_for(l, std::chrono::seconds(10),
+                    [&]() { return prs.remaining == 0; });
+  }
+  DeleteResourceMgr(resource_mgr_);
 }
 
 Status DirectSession::Run(

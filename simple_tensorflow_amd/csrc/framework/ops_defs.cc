@@ -158,6 +158,12 @@ REGISTER_OP("FusedBatchNormGrad").Input("y_backprop: T").Input("x: T").Input("sc
 // f32 scale/offset (the bf16 analog of FusedBatchNorm; reserve = 1/sqrt(var+eps)).
 REGISTER_OP("BatchNormMi").Input("x: T").Input("scale: float").Input("offset: float").Output("y: T").Output("batch_mean: float").Output("batch_variance: float").Output("reserve_inv_std: float").Attr("T: {float, bfloat16}").Attr("epsilon: float = 0.0001").Attr("fuse_relu: bool = false");
 REGISTER_OP("BatchNormAddReluMi").Input("x: T").Input("scale: float").Input("offset: float").Input("side: T").Output("y: T").Output("batch_mean: float").Output("batch_variance: float").Output("reserve_inv_std: float").Attr("T: {float, bfloat16}").Attr("epsilon: float = 0.0001");
+// Internal (graph/optimizer.cc FuseConvBnStats): a Conv2D that also returns
+// the per-channel sum and sum of squares of its output, sums = float[2*Cout],
+// and the two batch norms that take those instead of reading x again.
+REGISTER_OP("_Conv2DBnStats").Input("input: T").Input("filter: T").Output("output: T").Output("sums: float").Attr("T: {bfloat16}").Attr("strides: list(int)").Attr("use_cudnn_on_gpu: bool = true").Attr("padding: string").Attr("data_format: string = 'NHWC'");
+REGISTER_OP("_BatchNormMiStats").Input("x: T").Input("scale: float").Input("offset: float").Input("sums: float").Output("y: T").Output("batch_mean: float").Output("batch_variance: float").Output("reserve_inv_std: float").Attr("T: {bfloat16}").Attr("epsilon: float = 0.0001").Attr("fuse_relu: bool = false");
+REGISTER_OP("_BatchNormAddReluMiStats").Input("x: T").Input("scale: float").Input("offset: float").Input("side: T").Input("sums: float").Output("y: T").Output("batch_mean: float").Output("batch_variance: float").Output("reserve_inv_std: float").Attr("T: {bfloat16}").Attr("epsilon: float = 0.0001");
 REGISTER_OP("BatchNormAddReluMiGrad").Input("y_backprop: T").Input("x: T").Input("scale: float").Input("saved_mean: float").Input("saved_inv_std: float").Input("y_relu: T").Output("x_backprop: T").Output("scale_backprop: float").Output("offset_backprop: float").Output("side_backprop: T").Attr("T: {float, bfloat16}").Attr("epsilon: float = 0.0001");
 REGISTER_OP("BatchNormMiGrad").Input("y_backprop: T").Input("x: T").Input("scale: float").Input("saved_mean: float").Input("saved_inv_std: float").Input("y_relu: T").Output("x_backprop: T").Output("scale_backprop: float").Output("offset_backprop: float").Attr("T: {float, bfloat16}").Attr("epsilon: float = 0.0001").Attr("fuse_relu: bool = false");
 // Internal: scoped elementwise fusion output (graph/optimizer.cc emits it

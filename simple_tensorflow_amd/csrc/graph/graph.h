@@ -109,7 +109,10 @@ class Device;
 // Session-level graph optimization: common-subexpression elimination +
 // constant folding to fixpoint (graph/optimizer.cc). Nodes named in
 // `preserve` (feeds/fetches/targets) are never removed. `cpu` is the host
-// device used to execute foldable subgraphs. Returns nodes eliminated.
-int OptimizeGraph(Graph* g, Device* cpu, const std::set<std::string>& preserve);
+// device used to execute foldable subgraphs. `have_gpu`: placement will have
+// a GPU to put nodes on (the GPU-only fusions need one). Returns nodes
+// eliminated or fused.
+int OptimizeGraph(Graph* g, Device* cpu, const std::set<std::string>& preserve,
+                  bool have_gpu);
 
 }  // namespace stf

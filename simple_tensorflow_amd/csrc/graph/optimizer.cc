@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "framework/device.h"
 #include "framework/op_kernel.h"
 #include "graph/graph.h"
 #include "kernels/fused_ew.h"
@@ -433,12 +434,87 @@ int FuseElementwise(Graph* g, const std::set<std::string>& preserve) {
   return fused_total;
 }
 
+// ------------------ conv -> batch-norm statistics fusion --------------------
+// A bf16 GPU Conv2D whose output feeds exactly one bf16 batch norm becomes
+// _Conv2DBnStats, whose GEMM epilogue also produces the per-channel sum and
+// sum of squares; the batch norm becomes its _...Stats form, which takes them
+// as one more input instead of reading the conv output back to form them.
+// Both nodes are retyped in place, so names, attrs (the two pairs of ops
+// share them), every other consumer (the grad ops' x, mean, inv_std) and all
+// control edges stay as they are; the one new edge runs parallel to the
+// existing conv -> BN edge and so cannot close a cycle.
+
+// Placement runs after this pass, so "on the GPU" is judged from the request:
+// with a GPU present, an empty request or a GPU request. Returns "" for
+// anything else, and otherwise a key that is equal for equal requests. The
+// rewritten ops have GPU kernels only, so placement, which falls back to a
+// device that has a kernel, then keeps them on a GPU (a BN whose scale is a
+// ref input would otherwise follow its variable).
+std::string GpuPlacementKey(const Node* n, bool have_gpu) {
+  if (!have_gpu) return "";
+  if (n->def.device.empty()) return "default";
+  std::string req = CanonicalDevice(n->def.device);
+  return StrStartsWith(req, "GPU") ? req : "";
+}
+
+bool RetypeNode(Node* n, const std::string& op) {
+  const OpDef* od = OpRegistry::Global()->LookUp(op);
+  if (!od) return false;
+  NodeDef def = n->def;
+  def.op = op;
+  std::vector<DataType> in, out;
+  std::vector<bool> refs;
+  if (!InOutTypesForNode(def, *od, &in, &out, &refs).ok()) return false;
+  n->def = std::move(def);
+  n->op_def = od;
+  n->in_types = std::move(in);
+  n->out_types = std::move(out);
+  n->out_is_ref = std::move(refs);
+  return true;
+}
+
+int FuseConvBnStats(Graph* g, const std::set<std::string>& preserve,
+                    bool have_gpu) {
+  int fused = 0;
+  std::vector<Node*> nodes = g->nodes();
+  for (Node* conv : nodes) {
+    if (conv->op() != "Conv2D" || preserve.count(conv->name()) ||
+        conv->out_types[0] != DT_BFLOAT16)
+      continue;
+    std::string where = GpuPlacementKey(conv, have_gpu);
+    if (where.empty()) continue;
+    Node* bn = nullptr;
+    int n_bn = 0;
+    for (const Edge* e : conv->out_edges) {
+      if (e->IsControl() || e->dst_input != 0) continue;
+      if (e->dst->op() == "BatchNormMi" ||
+          e->dst->op() == "BatchNormAddReluMi") {
+        bn = e->dst;
+        ++n_bn;
+      }
+    }
+    if (n_bn != 1 || preserve.count(bn->name()) ||
+        bn->in_types[0] != DT_BFLOAT16 ||
+        GpuPlacementKey(bn, have_gpu) != where)
+      continue;
+    int sums_slot = bn->num_inputs();
+    if (!RetypeNode(conv, "_Conv2DBnStats")) continue;
+    if (!RetypeNode(bn, "_" + bn->op() + "Stats")) {
+      RetypeNode(conv, "Conv2D");
+      continue;
+    }
+    g->AddEdge(conv, 1, bn, sums_slot);
+    ++fused;
+  }
+  return fused;
+}
+
 }  // namespace
 
 // Runs CSE + constant folding to fixpoint (preserving feed/fetch/target
-// nodes). Returns number of nodes removed.
+// nodes), then the fusion passes. Returns number of nodes removed or fused.
 int OptimizeGraph(Graph* g, Device* cpu,
-                  const std::set<std::string>& preserve) {
+                  const std::set<std::string>& preserve, bool have_gpu) {
   static const bool disabled = getenv("STF_NO_GRAPH_OPT") != nullptr;
   if (disabled) return 0;
   int total = 0;
@@ -450,6 +526,9 @@ int OptimizeGraph(Graph* g, Device* cpu,
   }
   static const bool no_fusion = getenv("STF_NO_FUSION") != nullptr;
   if (!no_fusion) total += FuseElementwise(g, preserve);
+  // Read per call (A/B runs): one process can build a session each way.
+  if (getenv("STF_NO_CONV_BN_STATS") == nullptr)
+    total += FuseConvBnStats(g, preserve, have_gpu);
   return total;
 }
 

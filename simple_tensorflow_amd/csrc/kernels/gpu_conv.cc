@@ -94,9 +94,14 @@ static hipError_t TransposeBf16(OpKernelContext* ctx, const void* src,
   return stf_transpose2d(2, src, dst->raw_data(), rows, cols, s);
 }
 
+// Also _Conv2DBnStats (stats): the same conv, plus output 1 = float[2K], the
+// per-output-channel sum and sum of squares of the bf16 y, for the batch norm
+// that follows. On the 8-phase paths they come out of the GEMM epilogue;
+// every other path runs the conv as for Conv2D and then reads y once.
 class GpuConv2DOp : public OpKernel {
  public:
-  explicit GpuConv2DOp(OpKernelConstruction* c) : OpKernel(c) {
+  explicit GpuConv2DOp(OpKernelConstruction* c, bool stats = false)
+      : OpKernel(c), stats_(stats) {
     c->GetAttr("strides", &strides_);
     c->GetAttr("padding", &padding_);
   }
@@ -109,6 +114,11 @@ class GpuConv2DOp : public OpKernel {
     OP_REQUIRES_OK(ctx, GetConvGeom(x.shape(), w.shape(), strides_, padding_,
                                     &g));
     Tensor* y = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.K}));
+    float* sums = nullptr;
+    if (stats_) {
+      sums = ctx->allocate_output(1, TensorShape({2 * g.K}))->flat<float>();
+      OP_HIP_OK(ctx, ZeroF32(sums, 2 * g.K, s));
+    }
     if (!g.is_1x1_s1() && (g.C % 8) != 0 && x.dtype() == DT_BFLOAT16) {
       // stem: pad the channels of x and of w (zero in both)
       int64_t c = g.C;
@@ -147,8 +157,23 @@ class GpuConv2DOp : public OpKernel {
 
     // ---- run it ----
     Tensor wt;  // [K, rscp], for the NT kernels
+    // stats_ on an 8-phase path: the GEMM leaves partial[M/256][2][K] f32,
+    // whose column sums are the statistics
+    Tensor partial;
+    float* pt = nullptr;
+    auto sum_partials = [&]() {
+      return stf_bn_partial_sums(pt, sums, g.M() / 256, (int)(2 * g.K), s);
+    };
     if (path == kImplicit8Ph) {
       OP_HIP_OK(ctx, TransposeBf16(ctx, w.raw_data(), rscp, g.K, &wt, s));
+      if (stats_) {
+        pt = TilePartials(ctx, g, &partial);
+        OP_HIP_OK(ctx, stf_conv2d_fwd_8ph_stats(x.raw_data(), wt.raw_data(),
+                                                y->raw_data(), pt, ZeroPage(),
+                                                &sg, rscp, s));
+        OP_HIP_OK(ctx, sum_partials());
+        return;
+      }
       OP_HIP_OK(ctx, stf_conv2d_fwd_8ph(x.raw_data(), wt.raw_data(),
                                         y->raw_data(), ZeroPage(), &sg, rscp,
                                         s));
@@ -160,28 +185,56 @@ class GpuConv2DOp : public OpKernel {
       OP_HIP_OK(ctx, stf_conv2d_fwd_nt(x.raw_data(), w.raw_data(),
                                        y->raw_data(), ZeroPage(), &sg, rscp,
                                        s));
-      return;
-    }
-    Tensor col = x;  // 1x1/s1: x is the column matrix
-    if (!g.is_1x1_s1()) OP_HIP_OK(ctx, Im2Col(ctx, x, g, rscp, &col, s));
-    if (!fits_8ph && (g.K & 7) == 0) {
-      OP_HIP_OK(ctx, stf_gemm_bf16(col.raw_data(), w.raw_data(), y->raw_data(),
-                                   g.M(), g.K, rscp, rscp, g.K, 0, 1, s));
     } else {
-      // 8-phase-eligible shape (one small weight transpose buys the NT fast
-      // path for the big M=NPQ GEMM), or a cout the K-major staging cannot
-      // load 16B-aligned.
-      OP_HIP_OK(ctx, TransposeBf16(ctx, w.raw_data(), rscp, g.K, &wt, s));
-      OP_HIP_OK(ctx, stf_gemm_bf16_nt(col.raw_data(), wt.raw_data(),
-                                      y->raw_data(), g.M(), g.K, rscp, s));
+      Tensor col = x;  // 1x1/s1: x is the column matrix
+      if (!g.is_1x1_s1()) OP_HIP_OK(ctx, Im2Col(ctx, x, g, rscp, &col, s));
+      if (!fits_8ph && (g.K & 7) == 0) {
+        OP_HIP_OK(ctx, stf_gemm_bf16(col.raw_data(), w.raw_data(),
+                                     y->raw_data(), g.M(), g.K, rscp, rscp,
+                                     g.K, 0, 1, s));
+      } else {
+        // 8-phase-eligible shape (one small weight transpose buys the NT
+        // fast path for the big M=NPQ GEMM), or a cout the K-major staging
+        // cannot load 16B-aligned.
+        OP_HIP_OK(ctx, TransposeBf16(ctx, w.raw_data(), rscp, g.K, &wt, s));
+        // the gate under which stf_gemm_bf16_nt takes the 8-phase kernel
+        if (stats_ && fits_8ph && getenv("STF_NO_8PH") == nullptr) {
+          pt = TilePartials(ctx, g, &partial);
+          OP_HIP_OK(ctx, stf_gemm_bf16_8ph_stats(col.raw_data(),
+                                                 wt.raw_data(), y->raw_data(),
+                                                 pt, g.M(), g.K, rscp, rscp,
+                                                 rscp, s));
+          OP_HIP_OK(ctx, sum_partials());
+          return;
+        }
+        OP_HIP_OK(ctx, stf_gemm_bf16_nt(col.raw_data(), wt.raw_data(),
+                                        y->raw_data(), g.M(), g.K, rscp, s));
+      }
     }
+    // every other path: one read of y, as BatchNormMi would do
+    if (stats_)
+      OP_HIP_OK(ctx, stf_bn_sums(1, y->raw_data(), sums, g.M(), (int)g.K, s));
   }
 
  private:
+  static float* TilePartials(OpKernelContext* ctx, const GpuConvGeom& g,
+                             Tensor* t) {
+    *t = ctx->allocate_temp(DT_FLOAT, TensorShape({g.M() / 256, 2 * g.K}));
+    return t->flat<float>();
+  }
+
+  bool stats_;
   std::vector<int64_t> strides_;
   std::string padding_;
 };
 REGISTER_KERNEL_BUILDER(Name("Conv2D").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuConv2DOp);
+
+class GpuConv2DBnStatsOp : public GpuConv2DOp {
+ public:
+  explicit GpuConv2DBnStatsOp(OpKernelConstruction* c)
+      : GpuConv2DOp(c, true) {}
+};
+REGISTER_KERNEL_BUILDER(Name("_Conv2DBnStats").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuConv2DBnStatsOp);
 
 class GpuConv2DBackpropInputOp : public OpKernel {
  public:

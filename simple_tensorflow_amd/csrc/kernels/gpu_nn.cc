@@ -119,9 +119,13 @@ REGISTER_KERNEL_BUILDER(Name("SoftmaxCrossEntropyWithLogits").Device(DEVICE_GPU)
 // ---------------------------------------------------------------------------
 // batch norm
 // ---------------------------------------------------------------------------
+// given_sums (the _...Stats forms, fed by _Conv2DBnStats): the last input is
+// float[2c], the per-channel sum and sum of squares of x, so the pass that
+// reads x to form them is skipped.
 class GpuBatchNormMiOp : public OpKernel {
  public:
-  explicit GpuBatchNormMiOp(OpKernelConstruction* c) : OpKernel(c) {
+  explicit GpuBatchNormMiOp(OpKernelConstruction* c, bool given_sums = false)
+      : OpKernel(c), given_sums_(given_sums) {
     c->GetAttr("epsilon", &eps_);
     c->GetAttr("fuse_relu", &fuse_relu_);
   }
@@ -136,6 +140,18 @@ class GpuBatchNormMiOp : public OpKernel {
     Tensor* var = ctx->allocate_output(2, TensorShape({c}));
     Tensor* inv_std = ctx->allocate_output(3, TensorShape({c}));
     hipStream_t s = GPU_STREAM(ctx);
+    if (given_sums_) {
+      const Tensor& sums = ctx->input(3);
+      OP_REQUIRES(ctx, sums.NumElements() == 2 * c,
+                  errors::InvalidArgument("_BatchNormMiStats: sums size"));
+      OP_HIP_OK(ctx, stf_bn_fwd_acc(DtypeCode(x.dtype()), x.raw_data(),
+                                    scale.raw_data(), offset.raw_data(),
+                                    sums.flat<float>(), mean->flat<float>(),
+                                    var->flat<float>(),
+                                    inv_std->flat<float>(), y->raw_data(),
+                                    rows, c, eps_, fuse_relu_ ? 1 : 0, s));
+      return;
+    }
     Tensor acc = ctx->allocate_temp(DT_FLOAT, TensorShape({2 * c}));
     OP_HIP_OK(ctx, ZeroF32(acc.raw_data(), 2 * c, s));
     OP_HIP_OK(ctx, stf_bn_fwd(DtypeCode(x.dtype()), x.raw_data(),
@@ -147,9 +163,16 @@ class GpuBatchNormMiOp : public OpKernel {
   }
 
  private:
+  bool given_sums_;
   float eps_ = 1e-4f;
   bool fuse_relu_ = false;
 };
+class GpuBatchNormMiStatsOp : public GpuBatchNormMiOp {
+ public:
+  explicit GpuBatchNormMiStatsOp(OpKernelConstruction* c)
+      : GpuBatchNormMiOp(c, true) {}
+};
+REGISTER_KERNEL_BUILDER(Name("_BatchNormMiStats").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuBatchNormMiStatsOp);
 REGISTER_KERNEL_BUILDER(Name("BatchNormMi").Device(DEVICE_GPU).TypeConstraint<float>("T"), GpuBatchNormMiOp);
 REGISTER_KERNEL_BUILDER(Name("BatchNormMi").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuBatchNormMiOp);
 
@@ -157,7 +180,9 @@ REGISTER_KERNEL_BUILDER(Name("BatchNormMi").Device(DEVICE_GPU).TypeConstraint<bf
 // win is one elementwise pass instead of three over a [N,H,W,C] tensor).
 class GpuBatchNormAddReluMiOp : public OpKernel {
  public:
-  explicit GpuBatchNormAddReluMiOp(OpKernelConstruction* c) : OpKernel(c) {
+  explicit GpuBatchNormAddReluMiOp(OpKernelConstruction* c,
+                                   bool given_sums = false)
+      : OpKernel(c), given_sums_(given_sums) {
     c->GetAttr("epsilon", &eps_);
   }
   void Compute(OpKernelContext* ctx) override {
@@ -172,6 +197,20 @@ class GpuBatchNormAddReluMiOp : public OpKernel {
     Tensor* var = ctx->allocate_output(2, TensorShape({c}));
     Tensor* inv_std = ctx->allocate_output(3, TensorShape({c}));
     hipStream_t s = GPU_STREAM(ctx);
+    if (given_sums_) {  // see GpuBatchNormMiOp
+      const Tensor& sums = ctx->input(4);
+      OP_REQUIRES(ctx, sums.NumElements() == 2 * c,
+                  errors::InvalidArgument(
+                      "_BatchNormAddReluMiStats: sums size"));
+      OP_HIP_OK(ctx, stf_bn_add_relu_acc(x.raw_data(), side.raw_data(),
+                                         sums.flat<float>(),
+                                         mean->flat<float>(),
+                                         var->flat<float>(),
+                                         inv_std->flat<float>(),
+                                         scale.raw_data(), offset.raw_data(),
+                                         y->raw_data(), rows, c, eps_, s));
+      return;
+    }
     Tensor acc = ctx->allocate_temp(DT_FLOAT, TensorShape({2 * c}));
     OP_HIP_OK(ctx, ZeroF32(acc.raw_data(), 2 * c, s));
     // stats + finalize from the plain BN path, then the fused normalize
@@ -188,9 +227,16 @@ class GpuBatchNormAddReluMiOp : public OpKernel {
   }
 
  private:
+  bool given_sums_;
   float eps_ = 1e-4f;
 };
 REGISTER_KERNEL_BUILDER(Name("BatchNormAddReluMi").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuBatchNormAddReluMiOp);
+class GpuBatchNormAddReluMiStatsOp : public GpuBatchNormAddReluMiOp {
+ public:
+  explicit GpuBatchNormAddReluMiStatsOp(OpKernelConstruction* c)
+      : GpuBatchNormAddReluMiOp(c, true) {}
+};
+REGISTER_KERNEL_BUILDER(Name("_BatchNormAddReluMiStats").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuBatchNormAddReluMiStatsOp);
 
 class GpuBatchNormMiGradOp : public OpKernel {
  public:

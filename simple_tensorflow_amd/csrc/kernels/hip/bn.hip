@@ -388,6 +388,31 @@ __global__ void BnGradKernelV9(const __bf16* __restrict__ dy,
   }
 }
 
+// ---------------- column sums of per-tile partials ----------------
+// acc[j] += sum_t partial[t][j] for the [tiles][cols] f32 partials that the
+// 8-phase GEMM's STATS epilogue leaves. A block owns a 64-column strip
+// (blockIdx.x) and every gridDim.y-th group of 4 rows (blockIdx.y), so a
+// narrow matrix (the stem: 128 columns x 12544 tiles) still fills the GPU.
+// The four row lanes combine in LDS; one f32 atomic per block and column
+// then goes into the zeroed acc, a few KB in all.
+__global__ void BnPartialSumsKernel(const float* __restrict__ partial,
+                                    float* __restrict__ acc, int64_t tiles,
+                                    int cols) {
+  __shared__ float red[4][64];
+  int lane_c = threadIdx.x & 63, lane_r = threadIdx.x >> 6;
+  int col = blockIdx.x * 64 + lane_c;
+  float sum = 0.f;
+  if (col < cols)
+    for (int64_t t = (int64_t)blockIdx.y * 4 + lane_r; t < tiles;
+         t += (int64_t)gridDim.y * 4)
+      sum += partial[t * cols + col];
+  red[lane_r][lane_c] = sum;
+  __syncthreads();
+  if (lane_r == 0 && col < cols)
+    atomicAdd(&acc[col], (red[0][lane_c] + red[1][lane_c]) +
+                             (red[2][lane_c] + red[3][lane_c]));
+}
+
 // ---------------- dispatch ----------------
 // The one rule: bf16 with C % 8 == 0 runs the V9 kernels; f32 for any C and
 // bf16 with C % 8 != 0 run the scalar kernels.
@@ -396,10 +421,9 @@ inline bool UseV9(int dtype, int c) { return dtype != 0 && c % 8 == 0; }
 // Both reduction families keep two f32 arrays [c] in LDS.
 inline size_t BnLdsBytes(int c) { return (size_t)c * 2 * sizeof(float); }
 
-// Forward passes 1 + 2: batch statistics of x into mean/var/inv_std.
-void LaunchBnStats(int dtype, const void* x, float* acc, float* mean,
-                   float* var, float* inv_std, int64_t rows, int c, float eps,
-                   hipStream_t stream) {
+// Forward pass 1: column sums and sums of squares of x into acc.
+void LaunchBnSums(int dtype, const void* x, float* acc, int64_t rows, int c,
+                  hipStream_t stream) {
   if (UseV9(dtype, c)) {
     hipLaunchKernelGGL(BnStatsKernelV9, dim3(BnGridV9(c, rows)), dim3(256),
                        BnLdsBytes(c), stream, (const __bf16*)x, acc, rows, c);
@@ -410,26 +434,29 @@ void LaunchBnStats(int dtype, const void* x, float* acc, float* mean,
                          BnLdsBytes(c), stream, (const T*)x, acc, rows, c);
     });
   }
+}
+
+// Forward pass 2: acc -> mean/var/inv_std.
+void LaunchBnFinalize(const float* acc, float* mean, float* var,
+                      float* inv_std, int64_t rows, int c, float eps,
+                      hipStream_t stream) {
   hipLaunchKernelGGL(BnFinalizeKernel, dim3((c + 255) / 256), dim3(256), 0,
                      stream, acc, mean, var, inv_std, rows, c, eps);
 }
 
-}  // namespace
-
-extern "C" {
-
-hipError_t stf_bn_stats_only(int dtype, const void* x, float* acc, float* mean,
-                             float* var, float* inv_std, int64_t rows, int c,
-                             float eps, hipStream_t stream) {
-  LaunchBnStats(dtype, x, acc, mean, var, inv_std, rows, c, eps, stream);
-  return hipGetLastError();
+// Forward passes 1 + 2: batch statistics of x into mean/var/inv_std.
+void LaunchBnStats(int dtype, const void* x, float* acc, float* mean,
+                   float* var, float* inv_std, int64_t rows, int c, float eps,
+                   hipStream_t stream) {
+  LaunchBnSums(dtype, x, acc, rows, c, stream);
+  LaunchBnFinalize(acc, mean, var, inv_std, rows, c, eps, stream);
 }
 
-hipError_t stf_bn_fwd(int dtype, const void* x, const void* scale,
-                      const void* offset, float* acc, float* mean, float* var,
-                      float* inv_std, void* y, int64_t rows, int c, float eps,
-                      int fuse_relu, hipStream_t stream) {
-  LaunchBnStats(dtype, x, acc, mean, var, inv_std, rows, c, eps, stream);
+// Forward pass 3: normalize (+ optional relu).
+void LaunchBnNorm(int dtype, const void* x, const void* scale,
+                  const void* offset, const float* mean, const float* inv_std,
+                  void* y, int64_t rows, int c, int fuse_relu,
+                  hipStream_t stream) {
   DispatchBool(fuse_relu, [&](auto relu) {
     constexpr bool RELU = decltype(relu)::value;
     if (UseV9(dtype, c)) {
@@ -448,6 +475,56 @@ hipError_t stf_bn_fwd(int dtype, const void* x, const void* scale,
                          c);
     });
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+hipError_t stf_bn_stats_only(int dtype, const void* x, float* acc, float* mean,
+                             float* var, float* inv_std, int64_t rows, int c,
+                             float eps, hipStream_t stream) {
+  LaunchBnStats(dtype, x, acc, mean, var, inv_std, rows, c, eps, stream);
+  return hipGetLastError();
+}
+
+hipError_t stf_bn_fwd(int dtype, const void* x, const void* scale,
+                      const void* offset, float* acc, float* mean, float* var,
+                      float* inv_std, void* y, int64_t rows, int c, float eps,
+                      int fuse_relu, hipStream_t stream) {
+  LaunchBnStats(dtype, x, acc, mean, var, inv_std, rows, c, eps, stream);
+  LaunchBnNorm(dtype, x, scale, offset, mean, inv_std, y, rows, c, fuse_relu,
+               stream);
+  return hipGetLastError();
+}
+
+hipError_t stf_bn_fwd_acc(int dtype, const void* x, const void* scale,
+                          const void* offset, const float* acc, float* mean,
+                          float* var, float* inv_std, void* y, int64_t rows,
+                          int c, float eps, int fuse_relu,
+                          hipStream_t stream) {
+  LaunchBnFinalize(acc, mean, var, inv_std, rows, c, eps, stream);
+  LaunchBnNorm(dtype, x, scale, offset, mean, inv_std, y, rows, c, fuse_relu,
+               stream);
+  return hipGetLastError();
+}
+
+hipError_t stf_bn_sums(int dtype, const void* x, float* acc, int64_t rows,
+                       int c, hipStream_t stream) {
+  LaunchBnSums(dtype, x, acc, rows, c, stream);
+  return hipGetLastError();
+}
+
+hipError_t stf_bn_partial_sums(const float* partial, float* acc,
+                               int64_t tiles, int cols, hipStream_t stream) {
+  if (tiles < 1 || cols < 1) return hipErrorInvalidValue;
+  // About 1024 blocks, and no more row splits than leave a thread 4 rows.
+  int strips = (cols + 63) / 64;
+  int64_t splits = (tiles + 15) / 16;
+  int64_t cap = strips >= 1024 ? 1 : 1024 / strips;
+  if (splits > cap) splits = cap;
+  hipLaunchKernelGGL(BnPartialSumsKernel, dim3(strips, (uint32_t)splits),
+                     dim3(256), 0, stream, partial, acc, tiles, cols);
   return hipGetLastError();
 }
 
@@ -461,6 +538,17 @@ hipError_t stf_bn_add_relu(const void* x, const void* side, const float* mean,
                      (const __bf16*)side, mean, inv_std, (const float*)scale,
                      (const float*)offset, (__bf16*)y, rows, c);
   return hipGetLastError();
+}
+
+hipError_t stf_bn_add_relu_acc(const void* x, const void* side,
+                               const float* acc, float* mean, float* var,
+                               float* inv_std, const void* scale,
+                               const void* offset, void* y, int64_t rows,
+                               int c, float eps, hipStream_t stream) {
+  if (c % 8 != 0) return hipErrorInvalidValue;
+  LaunchBnFinalize(acc, mean, var, inv_std, rows, c, eps, stream);
+  return stf_bn_add_relu(x, side, mean, inv_std, scale, offset, y, rows, c,
+                         stream);
 }
 
 hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,

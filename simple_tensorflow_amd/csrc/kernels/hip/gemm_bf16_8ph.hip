@@ -63,11 +63,17 @@ __device__ __forceinline__ void Stage8(const AG& ag, int64_t row0, int64_t k0,
 }
 
 // NR = B fragments per wave; BN = 64*NR (wave grid fixed 2M x 4N).
-template <int NR, bool OUT_BF16, bool FUSE_RELU, class AG>
+// STATS (bf16 output only): the epilogue also writes this block's per-column
+// sum and sum of squares of the rounded tile to partial[M/256][2][N], so
+// batch norm needs no pass that reads C back. Without STATS `partial` is not
+// read and the device code is the same as it was before the flag existed.
+template <int NR, bool OUT_BF16, bool FUSE_RELU, class AG, bool STATS = false>
 __launch_bounds__(512) __global__ void Gemm256x8Ph(
     AG ag, const uint16_t* __restrict__ B, void* __restrict__ C,
     const float* __restrict__ bias, const uint16_t* __restrict__ side,
-    int64_t M, int64_t N, int64_t K, int64_t ldb) {
+    int64_t M, int64_t N, int64_t K, int64_t ldb,
+    float* __restrict__ partial) {
+  static_assert(!STATS || OUT_BF16, "STATS reads the rounded bf16 tile");
   constexpr int kBN = 64 * NR;
   constexpr int kABytes = kBM * kBK * 2;       // 32 KiB per slot
   constexpr int kBBytes = kBN * kBK * 2;       // per slot
@@ -235,13 +241,27 @@ __launch_bounds__(512) __global__ void Gemm256x8Ph(
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // STATS: 512*8 % kBN == 0, so this thread's 16B pieces all cover the
+    // same 8 columns, (tid*8) % kBN: one private f32 partial per column.
+    float p1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float p2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int p = 0; p < kBM * kBN / 8 / kThreads; ++p) {
       int sidx = (p * kThreads + tid) * 8;
       int r = sidx / kBN;
       int c = sidx % kBN;
       int64_t off = (m0 + r) * N + n0 + c;
-      if (side) {
+      if constexpr (STATS) {
+        __bf16 v[8];
+        *(ulong2*)v = *(ulong2*)(cbuf + sidx);
+        *(ulong2*)((uint16_t*)C + off) = *(ulong2*)v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float f = (float)v[e];
+          p1[e] += f;
+          p2[e] += f * f;
+        }
+      } else if (side) {
         // fused elementwise side add (residual-gradient accumulation):
         // one extra 16B load replaces a whole separate add pass
         __bf16 v[8], sv[8];
@@ -252,6 +272,34 @@ __launch_bounds__(512) __global__ void Gemm256x8Ph(
         *(ulong2*)((uint16_t*)C + off) = *(ulong2*)v;
       } else {
         *(ulong2*)((uint16_t*)C + off) = *(ulong2*)(cbuf + sidx);
+      }
+    }
+    if constexpr (STATS) {
+      // Reduce over the 64/NR threads that share a column window, through
+      // LDS: cbuf is dead once every thread has read its pieces. red[k][tid]
+      // with k = stat*8 + e; the row stride 520 (= 8 mod 64 banks) keeps
+      // both the tid-linear writes and the column-linear reads off shared
+      // banks. 16 * 520 floats = 32.5 KiB, inside every NR's allocation.
+      constexpr int kRedLd = kThreads + 8;
+      constexpr int kWin = kBN / 8;  // column windows; tid % kWin is ours
+      float* red = (float*)lds;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        red[e * kRedLd + tid] = p1[e];
+        red[(8 + e) * kRedLd + tid] = p2[e];
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (tid < 2 * kBN) {
+        int stat = tid / kBN, col = tid % kBN;
+        const float* src = red + (stat * 8 + (col & 7)) * kRedLd + (col >> 3);
+        float sum = 0.f;
+#pragma unroll
+        for (int g = 0; g < kThreads / kWin; ++g) sum += src[g * kWin];
+        partial[((int64_t)(bid / nbn) * 2 + stat) * N + n0 + col] = sum;
       }
     }
     return;
@@ -278,19 +326,20 @@ __launch_bounds__(512) __global__ void Gemm256x8Ph(
 // (all any caller asks for). OUT_BF16/FUSE_RELU and the bias argument stay
 // in the kernel: removing them would change tuned device code and needs GPU
 // timing. Caller has checked stf_gemm_bf16_8ph_ok(M, N, K).
-template <class AG>
+// STATS: also write the column sums of C to partial[M/256][2][N] (no side).
+template <bool STATS = false, class AG>
 hipError_t Launch8Ph(const AG& ag, const void* B, void* C, const void* side,
                      int64_t M, int64_t N, int64_t K, int64_t ldb,
-                     hipStream_t stream) {
+                     hipStream_t stream, float* partial = nullptr) {
   auto launch = [&](auto nr_c) {
     constexpr int NR = decltype(nr_c)::value;
     int64_t blocks = (M / kBM) * (N / (64 * NR));
     // LDS: A ring 64 KiB + B ring 2 * (BN*64*2) bytes.
     size_t shmem = 64 * 1024 + 2 * (size_t)(64 * NR) * kBK * 2;
-    hipLaunchKernelGGL((Gemm256x8Ph<NR, true, false, AG>),
+    hipLaunchKernelGGL((Gemm256x8Ph<NR, true, false, AG, STATS>),
                        dim3((uint32_t)blocks), dim3(kThreads), shmem, stream,
                        ag, (const uint16_t*)B, C, (const float*)nullptr,
-                       (const uint16_t*)side, M, N, K, ldb);
+                       (const uint16_t*)side, M, N, K, ldb, partial);
   };
   if (N % 256 == 0) launch(std::integral_constant<int, 4>{});
   else if (N % 128 == 0) launch(std::integral_constant<int, 2>{});
@@ -329,6 +378,28 @@ hipError_t stf_conv2d_fwd_8ph(const void* x, const void* wt, void* y,
     return hipErrorInvalidValue;
   return Launch8Ph(MakeConvAG(*g, x, zero16), wt, y, nullptr, M, g->cout,
                    rscp, rscp, stream);
+}
+
+// The two forward entry points with the STATS epilogue: same gates, plus
+// partial[M/256][2][N] f32, every element of which is written.
+hipError_t stf_gemm_bf16_8ph_stats(const void* A, const void* B, void* C,
+                                   float* partial, int64_t M, int64_t N,
+                                   int64_t K, int64_t lda, int64_t ldb,
+                                   hipStream_t stream) {
+  if (!stf_gemm_bf16_8ph_ok(M, N, K)) return hipErrorInvalidValue;
+  LinearAG ag{(const uint16_t*)A, lda};
+  return Launch8Ph<true>(ag, B, C, nullptr, M, N, K, ldb, stream, partial);
+}
+
+hipError_t stf_conv2d_fwd_8ph_stats(const void* x, const void* wt, void* y,
+                                    float* partial, const void* zero16,
+                                    const StfConvGeom* g, int64_t rscp,
+                                    hipStream_t stream) {
+  int64_t M = (int64_t)g->n * g->p * g->q;
+  if (!stf_gemm_bf16_8ph_ok(M, g->cout, rscp) || (g->c % 8) != 0)
+    return hipErrorInvalidValue;
+  return Launch8Ph<true>(MakeConvAG(*g, x, zero16), wt, y, nullptr, M,
+                         g->cout, rscp, rscp, stream, partial);
 }
 
 // Implicit-GEMM Conv2D backward-input for stride 1: dx[M=NHW, C] =

@@ -64,6 +64,13 @@ hipError_t stf_gemm_bf16_8ph_side(const void* A, const void* B, void* C,
                                   const void* side_bf16, int64_t M, int64_t N,
                                   int64_t K, int64_t lda, int64_t ldb,
                                   hipStream_t stream);
+// 8-phase NT GEMM, bf16 out, that also writes each 256-row tile's column
+// sums of the rounded C: partial[M/256][2][N] f32 ([t][0] = sum, [t][1] =
+// sum of squares), every element written. stf_bn_partial_sums adds them up.
+hipError_t stf_gemm_bf16_8ph_stats(const void* A, const void* B, void* C,
+                                   float* partial, int64_t M, int64_t N,
+                                   int64_t K, int64_t lda, int64_t ldb,
+                                   hipStream_t stream);
 hipError_t stf_gemm_f32_nt(const void* A, const void* B, void* C, int64_t M,
                            int64_t N, int64_t K, hipStream_t stream);
 
@@ -73,6 +80,12 @@ hipError_t stf_gemm_f32_nt(const void* A, const void* B, void* C, int64_t M,
 hipError_t stf_conv2d_fwd_8ph(const void* x, const void* wt, void* y,
                               const void* zero16, const StfConvGeom* g,
                               int64_t rscp, hipStream_t stream);
+// stf_conv2d_fwd_8ph with the column sums of y, as stf_gemm_bf16_8ph_stats:
+// partial[n*p*q/256][2][cout].
+hipError_t stf_conv2d_fwd_8ph_stats(const void* x, const void* wt, void* y,
+                                    float* partial, const void* zero16,
+                                    const StfConvGeom* g, int64_t rscp,
+                                    hipStream_t stream);
 hipError_t stf_conv2d_fwd_nt(const void* x, const void* w, void* y,
                              const void* zero16, const StfConvGeom* g,
                              int64_t rscp, hipStream_t stream);
@@ -173,6 +186,29 @@ hipError_t stf_bn_add_relu(const void* x, const void* side, const float* mean,
                            const float* inv_std, const void* scale,
                            const void* offset, void* y, int64_t rows, int c,
                            hipStream_t stream);
+// The forward from statistics that are already summed: acc is f32 [2c] =
+// per-channel sum, then sum of squares, of x (read only). stf_bn_fwd_acc is
+// stf_bn_fwd, and stf_bn_add_relu_acc is stf_bn_stats_only + stf_bn_add_relu,
+// without the pass that reads x to fill acc.
+hipError_t stf_bn_fwd_acc(int dtype, const void* x, const void* scale,
+                          const void* offset, const float* acc, float* mean,
+                          float* var, float* inv_std, void* y, int64_t rows,
+                          int c, float eps, int fuse_relu,
+                          hipStream_t stream);
+hipError_t stf_bn_add_relu_acc(const void* x, const void* side,
+                               const float* acc, float* mean, float* var,
+                               float* inv_std, const void* scale,
+                               const void* offset, void* y, int64_t rows,
+                               int c, float eps, hipStream_t stream);
+// The first pass of stf_bn_fwd alone: adds the column sums and sums of
+// squares of x into acc (zeroed f32 [2c]).
+hipError_t stf_bn_sums(int dtype, const void* x, float* acc, int64_t rows,
+                       int c, hipStream_t stream);
+// acc[j] += sum over t of partial[t][j], j < cols (zeroed f32 acc). With
+// cols = 2 * cout this turns the partial[tiles][2][cout] of the *_8ph_stats
+// GEMMs into the acc layout above.
+hipError_t stf_bn_partial_sums(const float* partial, float* acc,
+                               int64_t tiles, int cols, hipStream_t stream);
 // sum_dy (= doffset) and sum_dy_xhat (= dscale) are zeroed f32 [c] and are
 // accumulated in place. dside (optional, fuse_relu only): also receives the
 // ReLU-masked dy, y_relu > 0 ? dy : 0, the gradient of the residual branch.

@@ -117,7 +117,9 @@ Status DirectSession::BuildExecutors(const std::vector<std::string>& feeds,
     for (auto& f : feeds) preserve.insert(ParseTensorName(f).first);
     for (auto& f : fetches) preserve.insert(ParseTensorName(f).first);
     for (auto& t : targets) preserve.insert(ParseTensorName(t).first);
-    OptimizeGraph(graph.get(), devices_.LookUp("/cpu:0"), preserve);
+    bool have_gpu = false;
+    for (auto& d : devices_.devices()) have_gpu |= d->is_gpu();
+    OptimizeGraph(graph.get(), devices_.LookUp("/cpu:0"), preserve, have_gpu);
   }
 
   // ---- 1. Placement (before rewrite so feed recvs inherit devices). ----

@@ -28,7 +28,7 @@ class GpuBiasAddGradOp : public OpKernel {
   void Compute(OpKernelContext* ctx) override {
     const Tensor& dy = ctx->input(0);
     int c = (int)dy.dim_size(dy.dims() - 1);
-    int64_t rows = dy.NumElements() / c;
+    int64_t rows = c ? dy.NumElements() / c : 0;
     Tensor* db = ctx->allocate_output(0, TensorShape({c}));
     hipStream_t s = GPU_STREAM(ctx);
     Tensor scratch = ctx->allocate_temp(DT_FLOAT, TensorShape({c}));
@@ -50,7 +50,7 @@ class GpuSoftmaxOp : public OpKernel {
     const Tensor& x = ctx->input(0);
     Tensor* y = ctx->allocate_output(0, x.shape());
     int cols = (int)x.dim_size(x.dims() - 1);
-    int64_t rows = x.NumElements() / cols;
+    int64_t rows = cols ? x.NumElements() / cols : 0;
     OP_HIP_OK(ctx, stf_softmax(DtypeCode(x.dtype()), log_, x.raw_data(),
                                y->raw_data(), rows, cols, GPU_STREAM(ctx)));
   }

@@ -131,7 +131,15 @@ __global__ void SparseXentKernel(const T* __restrict__ logits,
   __syncthreads();
   sum = stat[1];
   float lsum = __logf(sum);
-  int lbl = (int)labels[r];
+  L lbl = labels[r];
+  if (lbl < 0 || lbl >= (L)cols) {
+    // a label outside [0, cols) has no class to score: NaN loss and a NaN
+    // backprop row, as the reference's GPU path gives
+    float nan = __builtin_nanf("");
+    for (int i = threadIdx.x; i < cols; i += blockDim.x) bp[i] = (T)nan;
+    if (threadIdx.x == 0 && loss) loss[r] = nan;
+    return;
+  }
   for (int i = threadIdx.x; i < cols; i += blockDim.x) {
     float logp = (float)row[i] - mx - lsum;
     bp[i] = (T)(__expf(logp) - (i == lbl ? 1.f : 0.f));
@@ -197,6 +205,7 @@ hipError_t stf_bias_add(int dtype, const void* x, const void* bias, void* y,
 // db_f32 must be zeroed
 hipError_t stf_bias_grad(int dtype, const void* dy, void* db_f32, int64_t rows,
                          int c, hipStream_t stream) {
+  if (rows <= 0 || c <= 0) return hipSuccess;  // db stays at its zeros
   uint32_t colb = (uint32_t)((c + 255) / 256);
   // enough row chunks to put ~512 blocks on the 256 CUs, but at least 4 rows
   // per chunk so the atomic traffic stays bounded
@@ -217,6 +226,7 @@ hipError_t stf_bias_grad(int dtype, const void* dy, void* db_f32, int64_t rows,
 
 hipError_t stf_softmax(int dtype, int log_sm, const void* x, void* y,
                        int64_t rows, int cols, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;  // empty input: nothing to launch
   DispatchDtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
     DispatchBool(log_sm, [&](auto log) {
@@ -231,6 +241,7 @@ hipError_t stf_softmax(int dtype, int log_sm, const void* x, void* y,
 hipError_t stf_sparse_xent(int dtype, const void* logits, const void* labels,
                            int labels_i32, void* loss_f32, void* backprop,
                            int64_t rows, int cols, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
   DispatchDtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
     DispatchBool(labels_i32, [&](auto i32) {
@@ -247,6 +258,7 @@ hipError_t stf_sparse_xent(int dtype, const void* logits, const void* labels,
 hipError_t stf_xent(int dtype, const void* logits, const void* labels,
                     void* loss_f32, void* backprop, int64_t rows, int cols,
                     hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
   DispatchDtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
     hipLaunchKernelGGL((XentKernel<T>), dim3((uint32_t)rows), dim3(256), 0,

@@ -238,6 +238,7 @@ REGISTER_OP("SetSize").Input("set_indices: int64").Input("set_values: T").Input(
 REGISTER_OP("QuantizeV2").Input("input: float").Input("min_range: float").Input("max_range: float").Output("output: T").Output("output_min: float").Output("output_max: float").Attr("T: {uint8} = uint8").Attr("mode: string = 'MIN_COMBINED'");
 REGISTER_OP("Dequantize").Input("input: T").Input("min_range: float").Input("max_range: float").Output("output: float").Attr("T: {uint8, int32} = uint8").Attr("mode: string = 'MIN_COMBINED'");
 REGISTER_OP("QuantizedMatMul").Input("a: T1").Input("b: T2").Input("min_a: float").Input("max_a: float").Input("min_b: float").Input("max_b: float").Output("out: Toutput").Output("min_out: float").Output("max_out: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("Toutput: {int32} = int32").Attr("transpose_a: bool = false").Attr("transpose_b: bool = false");
+REGISTER_OP("QuantizedConv2D").Input("input: T1").Input("filter: T2").Input("min_input: float").Input("max_input: float").Input("min_filter: float").Input("max_filter: float").Output("output: out_type").Output("min_output: float").Output("max_output: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("out_type: {int32} = int32").Attr("strides: list(int)").Attr("padding: string");
 REGISTER_OP("QuantizedRelu").Input("features: T").Input("min_features: float").Input("max_features: float").Output("activations: T").Output("min_activations: float").Output("max_activations: float").Attr("T: {uint8} = uint8");
 REGISTER_OP("QuantizeDownAndShrinkRange").Input("input: Tinput").Input("input_min: float").Input("input_max: float").Output("output: out_type").Output("output_min: float").Output("output_max: float").Attr("Tinput: {int32} = int32").Attr("out_type: {uint8} = uint8");
 REGISTER_OP("RequantizationRange").Input("input: Tinput").Input("input_min: float").Input("input_max: float").Output("output_min: float").Output("output_max: float").Attr("Tinput: {int32} = int32");

@@ -5,8 +5,11 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <string>
+#include <vector>
 
 #include "framework/op_kernel.h"
+#include "kernels/quantized_util.h"
 
 namespace stf {
 namespace {
@@ -44,7 +47,7 @@ class DequantizeOp : public OpKernel {
     Tensor* out = ctx->allocate_output(0, in.shape());
     float* o = out->flat<float>();
     if (in.dtype() == DT_UINT8) {
-      float step = (mx - mn) / 255.f;
+      float step = QuantStep(mn, mx);
       const uint8_t* p = in.flat<uint8_t>();
       for (int64_t i = 0; i < in.NumElements(); ++i)
         o[i] = mn + p[i] * step;
@@ -82,10 +85,10 @@ class QuantizedMatMulOp : public OpKernel {
     const uint8_t* bp = b.flat<uint8_t>();
     int32_t* op = out->flat<int32_t>();
     // zero points for MIN_COMBINED quint8
-    float sa = (max_a - min_a) / 255.f;
-    float sb = (max_b - min_b) / 255.f;
-    int32_t za = (int32_t)std::lround(-min_a / (sa != 0 ? sa : 1.f));
-    int32_t zb = (int32_t)std::lround(-min_b / (sb != 0 ? sb : 1.f));
+    float sa = QuantStep(min_a, max_a);
+    float sb = QuantStep(min_b, max_b);
+    int32_t za = QuantZeroPoint(min_a, max_a);
+    int32_t zb = QuantZeroPoint(min_b, max_b);
     for (int64_t m = 0; m < M; ++m)
       for (int64_t n = 0; n < N; ++n) {
         int64_t acc = 0;
@@ -97,11 +100,10 @@ class QuantizedMatMulOp : public OpKernel {
         op[m * N + n] = (int32_t)acc;
       }
     // float value of one output unit = sa * sb; int32 range maps to:
-    float unit = sa * sb;
     ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
-        (float)(-2147483648.0 * unit);
+        QuantProductMin(sa, sb);
     ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
-        (float)(2147483647.0 * unit);
+        QuantProductMax(sa, sb);
   }
 
  private:
@@ -109,6 +111,92 @@ class QuantizedMatMulOp : public OpKernel {
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedMatMul").Device(DEVICE_CPU),
                         QuantizedMatMulOp);
+
+// out[n,p,q,k] = sum over the taps inside the image of
+// (x - z_in) * (w - z_f), NHWC input, [R,S,C,K] filter, reduced to int32
+// modulo 2^32 (reference quantized_conv_ops.cc analog). Zero points and the
+// output range follow QuantizedMatMul.
+class QuantizedConv2DOp : public OpKernel {
+ public:
+  explicit QuantizedConv2DOp(OpKernelConstruction* c) : OpKernel(c) {
+    c->GetAttr("strides", &strides_);
+    c->GetAttr("padding", &padding_);
+  }
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& x = ctx->input(0);
+    const Tensor& w = ctx->input(1);
+    OP_REQUIRES(ctx, x.dims() == 4 && w.dims() == 4,
+                errors::InvalidArgument("QuantizedConv2D needs rank-4 input "
+                                        "and filter"));
+    OP_REQUIRES(ctx, strides_.size() == 4 && strides_[0] == 1 &&
+                         strides_[3] == 1,
+                errors::InvalidArgument("QuantizedConv2D strides must be "
+                                        "[1, sh, sw, 1]"));
+    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
+                errors::InvalidArgument("QuantizedConv2D padding must be "
+                                        "SAME or VALID"));
+    float min_x = ctx->input(2).flat<float>()[0];
+    float max_x = ctx->input(3).flat<float>()[0];
+    float min_w = ctx->input(4).flat<float>()[0];
+    float max_w = ctx->input(5).flat<float>()[0];
+    int64_t N = x.dim_size(0), H = x.dim_size(1), W = x.dim_size(2),
+            C = x.dim_size(3);
+    int64_t R = w.dim_size(0), S = w.dim_size(1), K = w.dim_size(3);
+    OP_REQUIRES(ctx, w.dim_size(2) == C,
+                errors::InvalidArgument("conv channel mismatch"));
+    int64_t sh = strides_[1], sw = strides_[2], P, Q, ph = 0, pw = 0;
+    if (padding_ == "SAME") {
+      P = (H + sh - 1) / sh;
+      Q = (W + sw - 1) / sw;
+      ph = std::max<int64_t>(0, (P - 1) * sh + R - H) / 2;
+      pw = std::max<int64_t>(0, (Q - 1) * sw + S - W) / 2;
+    } else {
+      P = (H - R) / sh + 1;
+      Q = (W - S) / sw + 1;
+    }
+    Tensor* out = ctx->allocate_output(0, TensorShape({N, P, Q, K}));
+    const uint8_t* xp = x.flat<uint8_t>();
+    const uint8_t* wp = w.flat<uint8_t>();
+    int32_t* op = out->flat<int32_t>();
+    float sx = QuantStep(min_x, max_x);
+    float sf = QuantStep(min_w, max_w);
+    int32_t zx = QuantZeroPoint(min_x, max_x);
+    int32_t zf = QuantZeroPoint(min_w, max_w);
+    std::vector<int64_t> acc(K);
+    for (int64_t n = 0; n < N; ++n)
+      for (int64_t p = 0; p < P; ++p)
+        for (int64_t q = 0; q < Q; ++q) {
+          std::fill(acc.begin(), acc.end(), 0);
+          for (int64_t r = 0; r < R; ++r) {
+            int64_t h = p * sh - ph + r;
+            if (h < 0 || h >= H) continue;
+            for (int64_t s = 0; s < S; ++s) {
+              int64_t wi = q * sw - pw + s;
+              if (wi < 0 || wi >= W) continue;
+              const uint8_t* xr = xp + ((n * H + h) * W + wi) * C;
+              const uint8_t* wr = wp + (r * S + s) * C * K;
+              for (int64_t c = 0; c < C; ++c) {
+                int64_t xv = (int32_t)xr[c] - zx;
+                for (int64_t k = 0; k < K; ++k)
+                  acc[k] += xv * ((int32_t)wr[c * K + k] - zf);
+              }
+            }
+          }
+          int32_t* o = op + ((n * P + p) * Q + q) * K;
+          for (int64_t k = 0; k < K; ++k) o[k] = (int32_t)acc[k];
+        }
+    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
+        QuantProductMin(sx, sf);
+    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
+        QuantProductMax(sx, sf);
+  }
+
+ private:
+  std::vector<int64_t> strides_;
+  std::string padding_;
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_CPU),
+                        QuantizedConv2DOp);
 
 class QuantizedReluOp : public OpKernel {
  public:
@@ -118,9 +206,8 @@ class QuantizedReluOp : public OpKernel {
     float mn = ctx->input(1).flat<float>()[0];
     float mx = ctx->input(2).flat<float>()[0];
     Tensor* out = ctx->allocate_output(0, in.shape());
-    float step = (mx - mn) / 255.f;
     // the quantized value representing 0.0
-    int32_t zero_q = (int32_t)std::lround(-mn / (step != 0 ? step : 1.f));
+    int32_t zero_q = QuantZeroPoint(mn, mx);
     const uint8_t* p = in.flat<uint8_t>();
     uint8_t* o = out->flat<uint8_t>();
     for (int64_t i = 0; i < in.NumElements(); ++i)

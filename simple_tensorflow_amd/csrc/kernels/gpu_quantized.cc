@@ -1,0 +1,253 @@
+// GPU OpKernels: the quantized family (QuantizeV2, Dequantize,
+// QuantizedMatMul, QuantizedConv2D, QuantizedRelu, RequantizationRange,
+// QuantizeDownAndShrinkRange) on kernels/hip/gemm_i8.hip and
+// kernels/hip/quantized.hip.
+//
+// The min/max ranges live in device memory on both sides of every op: no
+// argument is in host memory and nothing here reads a range value. The
+// kernels derive zero points and steps from the device scalars and write
+// the output ranges themselves, so a chain of quantized layers has no
+// device-to-host sync and replays inside a captured step.
+#include "kernels/gpu_common.h"
+
+namespace stf {
+namespace {
+
+const float* F32(const Tensor& t) { return (const float*)t.raw_data(); }
+
+float* ScalarOut(OpKernelContext* ctx, int i) {
+  return (float*)ctx->allocate_output(i, TensorShape({}))->raw_data();
+}
+
+int64_t RoundUp64(int64_t k) { return (k + 63) & ~int64_t(63); }
+
+class GpuQuantizeV2Op : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    OP_HIP_OK(ctx, stf_quantize_v2(F32(in), F32(ctx->input(1)),
+                                   F32(ctx->input(2)),
+                                   (uint8_t*)out->raw_data(), omn, omx,
+                                   in.NumElements(), GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizeV2").Device(DEVICE_GPU),
+                        GpuQuantizeV2Op);
+
+class GpuDequantizeOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    OP_HIP_OK(ctx, stf_dequantize(in.dtype() == DT_UINT8 ? 0 : 1,
+                                  in.raw_data(), F32(ctx->input(1)),
+                                  F32(ctx->input(2)),
+                                  (float*)out->raw_data(), in.NumElements(),
+                                  GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("Dequantize").Device(DEVICE_GPU),
+                        GpuDequantizeOp);
+
+// Packs a u8 operand for the i8 GEMM: element (row, k) at src[row * sr +
+// k * sk] -> s8 [rows][K rounded up to 64]. With sums, also allocates and
+// fills the [1 or 1 + taps][rows] int32 sums of the packed rows.
+hipError_t Pack(OpKernelContext* ctx, const void* src, int64_t sr, int64_t sk,
+                int64_t rows, int64_t K, int taps, Tensor* packed,
+                Tensor* sums, hipStream_t s) {
+  *packed = ctx->allocate_temp(DT_UINT8, TensorShape({rows, RoundUp64(K)}));
+  int32_t* sp = nullptr;
+  if (sums) {
+    int64_t n = (taps > 1 ? 1 + taps : 1) * rows;
+    *sums = ctx->allocate_temp(DT_INT32, TensorShape({n}));
+    sp = (int32_t*)sums->raw_data();
+    hipError_t e = hipMemsetAsync(sp, 0, n * sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+  }
+  return stf_pack_i8(src, sr, sk, rows, K, packed->raw_data(), sp, taps, s);
+}
+
+class GpuQuantizedMatMulOp : public OpKernel {
+ public:
+  explicit GpuQuantizedMatMulOp(OpKernelConstruction* c) : OpKernel(c) {
+    c->GetAttr("transpose_a", &ta_);
+    c->GetAttr("transpose_b", &tb_);
+  }
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& a = ctx->input(0);
+    const Tensor& b = ctx->input(1);
+    hipStream_t s = GPU_STREAM(ctx);
+    OP_REQUIRES(ctx, a.dims() == 2 && b.dims() == 2,
+                errors::InvalidArgument("QuantizedMatMul needs matrices"));
+    int64_t M = ta_ ? a.dim_size(1) : a.dim_size(0);
+    int64_t K = ta_ ? a.dim_size(0) : a.dim_size(1);
+    int64_t N = tb_ ? b.dim_size(0) : b.dim_size(1);
+    OP_REQUIRES(ctx, K == (tb_ ? b.dim_size(1) : b.dim_size(0)),
+                errors::InvalidArgument("QuantizedMatMul inner dim mismatch"));
+    Tensor* out = ctx->allocate_output(0, TensorShape({M, N}));
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    // B -> [N][Kp] s8 with its column sums; stored [K,N] unless transpose_b
+    Tensor bp, bsums;
+    OP_HIP_OK(ctx, Pack(ctx, b.raw_data(), tb_ ? K : 1, tb_ ? 1 : N, N, K, 1,
+                        &bp, &bsums, s));
+    // A is staged straight from the u8 matrix when its rows are k-contiguous
+    // and 16-byte aligned; otherwise it goes through the packer too.
+    const void* ap = a.raw_data();
+    Tensor a_packed;
+    bool pack_a = ta_ || (K & 15) != 0;
+    if (pack_a) {
+      OP_HIP_OK(ctx, Pack(ctx, a.raw_data(), ta_ ? 1 : K, ta_ ? M : 1, M, K,
+                          1, &a_packed, nullptr, s));
+      ap = a_packed.raw_data();
+    }
+    OP_HIP_OK(ctx, stf_gemm_i8(ap, pack_a ? 1 : 0, bp.raw_data(),
+                               (const int32_t*)bsums.raw_data(),
+                               F32(ctx->input(2)), F32(ctx->input(3)),
+                               F32(ctx->input(4)), F32(ctx->input(5)),
+                               (int32_t*)out->raw_data(), omn, omx, M, N, K,
+                               s));
+  }
+
+ private:
+  bool ta_ = false, tb_ = false;
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedMatMul").Device(DEVICE_GPU),
+                        GpuQuantizedMatMulOp);
+
+class GpuQuantizedConv2DOp : public OpKernel {
+ public:
+  explicit GpuQuantizedConv2DOp(OpKernelConstruction* c) : OpKernel(c) {
+    c->GetAttr("strides", &strides_);
+    c->GetAttr("padding", &padding_);
+  }
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& x = ctx->input(0);
+    const Tensor& w = ctx->input(1);
+    hipStream_t s = GPU_STREAM(ctx);
+    OP_REQUIRES(ctx, x.dims() == 4 && w.dims() == 4,
+                errors::InvalidArgument("QuantizedConv2D needs rank-4 input "
+                                        "and filter"));
+    OP_REQUIRES(ctx, strides_.size() == 4 && strides_[0] == 1 &&
+                         strides_[3] == 1,
+                errors::InvalidArgument("QuantizedConv2D strides must be "
+                                        "[1, sh, sw, 1]"));
+    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
+                errors::InvalidArgument("QuantizedConv2D padding must be "
+                                        "SAME or VALID"));
+    OP_REQUIRES(ctx, w.dim_size(2) == x.dim_size(3),
+                errors::InvalidArgument("conv channel mismatch"));
+    StfConvGeom g;
+    g.n = (int)x.dim_size(0);
+    g.h = (int)x.dim_size(1);
+    g.w = (int)x.dim_size(2);
+    g.c = (int)x.dim_size(3);
+    g.r = (int)w.dim_size(0);
+    g.s = (int)w.dim_size(1);
+    g.cout = w.dim_size(3);
+    g.sh = (int)strides_[1];
+    g.sw = (int)strides_[2];
+    if (padding_ == "SAME") {
+      g.p = (g.h + g.sh - 1) / g.sh;
+      g.q = (g.w + g.sw - 1) / g.sw;
+      g.ph = std::max(0, (g.p - 1) * g.sh + g.r - g.h) / 2;
+      g.pw = std::max(0, (g.q - 1) * g.sw + g.s - g.w) / 2;
+    } else {
+      g.p = (g.h - g.r) / g.sh + 1;
+      g.q = (g.w - g.s) / g.sw + 1;
+      g.ph = g.pw = 0;
+    }
+    Tensor* y = ctx->allocate_output(
+        0, TensorShape({(int64_t)g.n, (int64_t)g.p, (int64_t)g.q, g.cout}));
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    int64_t rsc = (int64_t)g.r * g.s * g.c;
+    // filter [rsc, cout] -> [cout][Kp] s8 with the per-tap sums
+    Tensor wp, wsums;
+    OP_HIP_OK(ctx, Pack(ctx, w.raw_data(), 1, g.cout, g.cout, rsc,
+                        g.r * g.s, &wp, &wsums, s));
+    const void* ap = x.raw_data();
+    Tensor col;
+    bool implicit = (g.c & 15) == 0;
+    if (!implicit) {
+      // small-channel stems: materialized s8 column matrix
+      int64_t kp = RoundUp64(rsc);
+      col = ctx->allocate_temp(
+          DT_UINT8, TensorShape({(int64_t)g.n * g.p * g.q, kp}));
+      OP_HIP_OK(ctx, stf_im2col_i8(x.raw_data(), col.raw_data(), &g, kp, s));
+      ap = col.raw_data();
+    }
+    OP_HIP_OK(ctx, stf_conv2d_i8(ap, implicit ? 1 : 0, wp.raw_data(),
+                                 (const int32_t*)wsums.raw_data(),
+                                 F32(ctx->input(2)), F32(ctx->input(3)),
+                                 F32(ctx->input(4)), F32(ctx->input(5)),
+                                 (int32_t*)y->raw_data(), omn, omx, &g, s));
+  }
+
+ private:
+  std::vector<int64_t> strides_;
+  std::string padding_;
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_GPU),
+                        GpuQuantizedConv2DOp);
+
+class GpuQuantizedReluOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    OP_HIP_OK(ctx, stf_quantized_relu((const uint8_t*)in.raw_data(),
+                                      F32(ctx->input(1)), F32(ctx->input(2)),
+                                      (uint8_t*)out->raw_data(), omn, omx,
+                                      in.NumElements(), GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedRelu").Device(DEVICE_GPU),
+                        GpuQuantizedReluOp);
+
+class GpuRequantizationRangeOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    float* omn = ScalarOut(ctx, 0);
+    float* omx = ScalarOut(ctx, 1);
+    Tensor lohi = ctx->allocate_temp(DT_INT32, TensorShape({2}));
+    OP_HIP_OK(ctx, stf_requantization_range(
+                       (const int32_t*)in.raw_data(), F32(ctx->input(1)),
+                       F32(ctx->input(2)), (int32_t*)lohi.raw_data(), omn,
+                       omx, in.NumElements(), GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("RequantizationRange").Device(DEVICE_GPU),
+                        GpuRequantizationRangeOp);
+
+class GpuQuantizeDownAndShrinkRangeOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    Tensor lohi = ctx->allocate_temp(DT_INT32, TensorShape({2}));
+    OP_HIP_OK(ctx, stf_quantize_down((const int32_t*)in.raw_data(),
+                                     F32(ctx->input(1)), F32(ctx->input(2)),
+                                     (int32_t*)lohi.raw_data(),
+                                     (uint8_t*)out->raw_data(), omn, omx,
+                                     in.NumElements(), GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizeDownAndShrinkRange").Device(DEVICE_GPU),
+                        GpuQuantizeDownAndShrinkRangeOp);
+
+}  // namespace
+}  // namespace stf

@@ -1,0 +1,310 @@
+// Elementwise and range kernels of the quantized ops: QuantizeV2,
+// Dequantize, QuantizedRelu, RequantizationRange, QuantizeDownAndShrinkRange.
+//
+// Every output is bit-equal to kernels/cpu_quantized.cc: the same IEEE
+// operations in the same order and precision (f32 for the quint8 paths, f64
+// for the qint32 paths), with floating-point contraction off so that
+// mn + q * step is never fused into an FMA. The ranges are device scalars,
+// read through pointers and written by the kernels, so a chain of quantized
+// layers never synchronises with the host.
+#include "hip_common.h"
+#include "kernels/quantized_util.h"
+#include "stf_kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+__device__ __forceinline__ uint8_t QuantizeOne(float x, float mn,
+                                               float scale) {
+  float q = roundf((x - mn) * scale);
+  float lo = 0.f < q ? q : 0.f;          // std::max(0.f, q)
+  float v = lo < 255.f ? lo : 255.f;     // std::min(255.f, .)
+  return (uint8_t)v;
+}
+
+__global__ void QuantizeV2Kernel(const float* __restrict__ x,
+                                 const float* __restrict__ mnp,
+                                 const float* __restrict__ mxp,
+                                 uint8_t* __restrict__ y,
+                                 float* __restrict__ out_mn,
+                                 float* __restrict__ out_mx, int64_t n) {
+  float mn = mnp[0], mx = mxp[0];
+  if (mx <= mn) mx = mn + 1e-6f;
+  float scale = 255.f / (mx - mn);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = mn;
+    out_mx[0] = mx;
+  }
+  int64_t n4 = n / 4;
+  for (int64_t i = tid; i < n4; i += stride) {
+    float4 v = ((const float4*)x)[i];
+    uint32_t w = (uint32_t)QuantizeOne(v.x, mn, scale) |
+                 (uint32_t)QuantizeOne(v.y, mn, scale) << 8 |
+                 (uint32_t)QuantizeOne(v.z, mn, scale) << 16 |
+                 (uint32_t)QuantizeOne(v.w, mn, scale) << 24;
+    ((uint32_t*)y)[i] = w;
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
+    y[i] = QuantizeOne(x[i], mn, scale);
+}
+
+__global__ void DequantizeU8Kernel(const uint8_t* __restrict__ x,
+                                   const float* __restrict__ mnp,
+                                   const float* __restrict__ mxp,
+                                   float* __restrict__ y, int64_t n) {
+  float mn = mnp[0];
+  float step = stf::QuantStep(mn, mxp[0]);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t n4 = n / 4;
+  for (int64_t i = tid; i < n4; i += stride) {
+    uint32_t w = ((const uint32_t*)x)[i];
+    float4 o;
+    o.x = mn + (float)(w & 0xff) * step;
+    o.y = mn + (float)((w >> 8) & 0xff) * step;
+    o.z = mn + (float)((w >> 16) & 0xff) * step;
+    o.w = mn + (float)(w >> 24) * step;
+    ((float4*)y)[i] = o;
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
+    y[i] = mn + (float)x[i] * step;
+}
+
+__device__ __forceinline__ float DequantizeI32One(int32_t p, double scale,
+                                                  float mn) {
+  return (float)(((double)p + 2147483648.0) * scale + mn);
+}
+
+__global__ void DequantizeI32Kernel(const int32_t* __restrict__ x,
+                                    const float* __restrict__ mnp,
+                                    const float* __restrict__ mxp,
+                                    float* __restrict__ y, int64_t n) {
+  float mn = mnp[0];
+  double scale = ((double)mxp[0] - mn) / 4294967295.0;
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t n4 = n / 4;
+  for (int64_t i = tid; i < n4; i += stride) {
+    int4 v = ((const int4*)x)[i];
+    float4 o;
+    o.x = DequantizeI32One(v.x, scale, mn);
+    o.y = DequantizeI32One(v.y, scale, mn);
+    o.z = DequantizeI32One(v.z, scale, mn);
+    o.w = DequantizeI32One(v.w, scale, mn);
+    ((float4*)y)[i] = o;
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
+    y[i] = DequantizeI32One(x[i], scale, mn);
+}
+
+// max per byte of the four u8 lanes of a word against one floor value
+__device__ __forceinline__ uint32_t MaxU8x4(uint32_t w, int32_t floor_q) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    int32_t p = (int32_t)((w >> (8 * b)) & 0xff);
+    o |= (uint32_t)(uint8_t)(p > floor_q ? p : floor_q) << (8 * b);
+  }
+  return o;
+}
+
+__global__ void QuantizedReluKernel(const uint8_t* __restrict__ x,
+                                    const float* __restrict__ mnp,
+                                    const float* __restrict__ mxp,
+                                    uint8_t* __restrict__ y,
+                                    float* __restrict__ out_mn,
+                                    float* __restrict__ out_mx, int64_t n) {
+  float mn = mnp[0], mx = mxp[0];
+  int32_t zero_q = stf::QuantZeroPoint(mn, mx);
+  int32_t floor_q = zero_q > 0 ? zero_q : 0;
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = mn;
+    out_mx[0] = mx;
+  }
+  int64_t n16 = n / 16;
+  for (int64_t i = tid; i < n16; i += stride) {
+    uint4 v = ((const uint4*)x)[i];
+    v.x = MaxU8x4(v.x, floor_q);
+    v.y = MaxU8x4(v.y, floor_q);
+    v.z = MaxU8x4(v.z, floor_q);
+    v.w = MaxU8x4(v.w, floor_q);
+    ((uint4*)y)[i] = v;
+  }
+  for (int64_t i = n16 * 16 + tid; i < n; i += stride) {
+    int32_t p = x[i];
+    y[i] = (uint8_t)(p > floor_q ? p : floor_q);
+  }
+}
+
+// lohi[0] = min(lohi[0], min x), lohi[1] = max(lohi[1], max x); the caller
+// zeroes lohi on the stream first, which is the CPU loops' starting value.
+__global__ void MinMaxI32Kernel(const int32_t* __restrict__ x,
+                                int32_t* __restrict__ lohi, int64_t n) {
+  __shared__ int32_t slo[4], shi[4];
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int32_t lo = 0, hi = 0;
+  int64_t n4 = n / 4;
+  for (int64_t i = tid; i < n4; i += stride) {
+    int4 v = ((const int4*)x)[i];
+    lo = min(lo, min(min(v.x, v.y), min(v.z, v.w)));
+    hi = max(hi, max(max(v.x, v.y), max(v.z, v.w)));
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride) {
+    lo = min(lo, x[i]);
+    hi = max(hi, x[i]);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = min(lo, __shfl_xor(lo, off));
+    hi = max(hi, __shfl_xor(hi, off));
+  }
+  int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) {
+    slo[wid] = lo;
+    shi[wid] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    lo = min(min(slo[0], slo[1]), min(slo[2], slo[3]));
+    hi = max(max(shi[0], shi[1]), max(shi[2], shi[3]));
+    if (lo < 0) atomicMin(&lohi[0], lo);
+    if (hi > 0) atomicMax(&lohi[1], hi);
+  }
+}
+
+__global__ void RequantRangeKernel(const int32_t* __restrict__ lohi,
+                                   const float* __restrict__ mnp,
+                                   const float* __restrict__ mxp,
+                                   float* __restrict__ out_mn,
+                                   float* __restrict__ out_mx) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double unit = ((double)mxp[0] - mnp[0]) / 4294967295.0;
+  out_mn[0] = (float)(lohi[0] * unit);
+  out_mx[0] = (float)(lohi[1] * unit);
+}
+
+// The CPU code takes min/max over x[i] * unit starting from 0.0. x -> x *
+// unit is monotone (either way, by the sign of unit), so the extremes are
+// reached at the integer extremes.
+__device__ __forceinline__ void ShrunkRange(const int32_t* lohi, double unit,
+                                            double* lo, double* hi) {
+  double a = lohi[0] * unit, b = lohi[1] * unit;
+  double l = 0, h = 0;
+  l = a < l ? a : l;
+  l = b < l ? b : l;
+  h = h < a ? a : h;
+  h = h < b ? b : h;
+  if (h <= l) h = l + 1e-6;
+  *lo = l;
+  *hi = h;
+}
+
+__device__ __forceinline__ uint8_t QuantizeDownOne(int32_t p, double unit,
+                                                   double lo, double scale) {
+  double v = round((p * unit - lo) * scale);
+  double m = 0.0 < v ? v : 0.0;
+  m = m < 255.0 ? m : 255.0;
+  return (uint8_t)m;
+}
+
+__global__ void QuantizeDownKernel(const int32_t* __restrict__ x,
+                                   const int32_t* __restrict__ lohi,
+                                   const float* __restrict__ mnp,
+                                   const float* __restrict__ mxp,
+                                   uint8_t* __restrict__ y,
+                                   float* __restrict__ out_mn,
+                                   float* __restrict__ out_mx, int64_t n) {
+  double unit = ((double)mxp[0] - mnp[0]) / 4294967295.0;
+  double lo, hi;
+  ShrunkRange(lohi, unit, &lo, &hi);
+  double scale = 255.0 / (hi - lo);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = (float)lo;
+    out_mx[0] = (float)hi;
+  }
+  int64_t n4 = n / 4;
+  for (int64_t i = tid; i < n4; i += stride) {
+    int4 v = ((const int4*)x)[i];
+    uint32_t w = (uint32_t)QuantizeDownOne(v.x, unit, lo, scale) |
+                 (uint32_t)QuantizeDownOne(v.y, unit, lo, scale) << 8 |
+                 (uint32_t)QuantizeDownOne(v.z, unit, lo, scale) << 16 |
+                 (uint32_t)QuantizeDownOne(v.w, unit, lo, scale) << 24;
+    ((uint32_t*)y)[i] = w;
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
+    y[i] = QuantizeDownOne(x[i], unit, lo, scale);
+}
+
+hipError_t MinMaxI32(const int32_t* x, int32_t* lohi, int64_t n,
+                     hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(lohi, 0, 2 * sizeof(int32_t), stream);
+  if (e != hipSuccess) return e;
+  if (n > 0)
+    hipLaunchKernelGGL(MinMaxI32Kernel, ElemwiseGrid(n), dim3(256), 0, stream,
+                       x, lohi, n);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" hipError_t stf_quantize_v2(const float* x, const float* mn,
+                                      const float* mx, uint8_t* y,
+                                      float* out_mn, float* out_mx, int64_t n,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(QuantizeV2Kernel, ElemwiseGrid(n), dim3(256), 0, stream,
+                     x, mn, mx, y, out_mn, out_mx, n);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_dequantize(int in_i32, const void* x,
+                                     const float* mn, const float* mx,
+                                     float* y, int64_t n,
+                                     hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (in_i32)
+    hipLaunchKernelGGL(DequantizeI32Kernel, ElemwiseGrid(n), dim3(256), 0,
+                       stream, (const int32_t*)x, mn, mx, y, n);
+  else
+    hipLaunchKernelGGL(DequantizeU8Kernel, ElemwiseGrid(n), dim3(256), 0,
+                       stream, (const uint8_t*)x, mn, mx, y, n);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantized_relu(const uint8_t* x, const float* mn,
+                                         const float* mx, uint8_t* y,
+                                         float* out_mn, float* out_mx,
+                                         int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(QuantizedReluKernel, ElemwiseGrid(n, 256, 16), dim3(256),
+                     0, stream, x, mn, mx, y, out_mn, out_mx, n);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_requantization_range(
+    const int32_t* x, const float* mn, const float* mx, int32_t* lohi,
+    float* out_mn, float* out_mx, int64_t n, hipStream_t stream) {
+  hipError_t e = MinMaxI32(x, lohi, n, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(RequantRangeKernel, dim3(1), dim3(64), 0, stream, lohi,
+                     mn, mx, out_mn, out_mx);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantize_down(const int32_t* x, const float* mn,
+                                        const float* mx, int32_t* lohi,
+                                        uint8_t* y, float* out_mn,
+                                        float* out_mx, int64_t n,
+                                        hipStream_t stream) {
+  hipError_t e = MinMaxI32(x, lohi, n, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(QuantizeDownKernel, ElemwiseGrid(n), dim3(256), 0,
+                     stream, x, lohi, mn, mx, y, out_mn, out_mx, n);
+  return hipGetLastError();
+}

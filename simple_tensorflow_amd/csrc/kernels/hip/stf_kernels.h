@@ -112,6 +112,67 @@ hipError_t stf_conv2d_dx_8ph(const void* dy, const void* wt, void* dx,
                              const StfConvGeom* g, int64_t rscp,
                              hipStream_t stream);
 
+// ---- gemm_i8.hip ----
+// Quantized quint8 x quint8 -> qint32 on the i8 MFMA. Ranges are device f32
+// scalars: zero points are derived on the device, min_out/max_out are
+// written by the kernel. Operands reach the MFMA as s8 = u8 ^ 0x80, k
+// contiguous, K rounded up to Kp = a multiple of 64 with a zero tail.
+//
+// Packs a u8 matrix whose element (row, k) is src[row * row_stride +
+// k * k_stride] into dst_s8 [rows][Kp]. sums (optional, zeroed int32):
+// [0][row] = sum over k of the packed row; with taps > 1 the buffer is
+// [1 + taps][rows] and [1 + t][row] is the part of that sum in k-range
+// [t * K/taps, (t+1) * K/taps).
+hipError_t stf_pack_i8(const void* src_u8, int64_t row_stride,
+                       int64_t k_stride, int64_t rows, int64_t K,
+                       void* dst_s8, int32_t* sums, int taps,
+                       hipStream_t stream);
+// NHWC u8 image -> packed column matrix [n*p*q][kp], kp = r*s*c rounded up
+// to 64; out-of-image taps are 0 in the s8 domain.
+hipError_t stf_im2col_i8(const void* x_u8, void* col_s8, const StfConvGeom* g,
+                         int64_t kp, hipStream_t stream);
+// C[M,N] = sum_k (A - z_a)(B - z_b) mod 2^32. A: packed [M][Kp] (a_packed),
+// or raw u8 [M][K] with K % 16 == 0. Bp: packed [N][Kp]; bsums: its sums.
+hipError_t stf_gemm_i8(const void* A, int a_packed, const void* Bp,
+                       const int32_t* bsums, const float* min_a,
+                       const float* max_a, const float* min_b,
+                       const float* max_b, int32_t* C, float* min_out,
+                       float* max_out, int64_t M, int64_t N, int64_t K,
+                       hipStream_t stream);
+// Conv2D over the in-image taps only. implicit: x_or_col is the NHWC u8
+// image (c % 16 == 0) and the column matrix is generated in staging; else
+// it is the stf_im2col_i8 matrix. wp: the [r*s*c, cout] filter packed to
+// [cout][Kp]; wsums: its sums with taps = r*s.
+hipError_t stf_conv2d_i8(const void* x_or_col, int implicit, const void* wp,
+                         const int32_t* wsums, const float* min_x,
+                         const float* max_x, const float* min_w,
+                         const float* max_w, int32_t* y, float* min_out,
+                         float* max_out, const StfConvGeom* g,
+                         hipStream_t stream);
+
+// ---- quantized.hip ----
+// Bit-equal to the CPU kernels (kernels/cpu_quantized.cc). Ranges are device
+// f32 scalars in and out.
+hipError_t stf_quantize_v2(const float* x, const float* mn, const float* mx,
+                           uint8_t* y, float* out_mn, float* out_mx,
+                           int64_t n, hipStream_t stream);
+// in_i32: qint32 carrier, else quint8.
+hipError_t stf_dequantize(int in_i32, const void* x, const float* mn,
+                          const float* mx, float* y, int64_t n,
+                          hipStream_t stream);
+hipError_t stf_quantized_relu(const uint8_t* x, const float* mn,
+                              const float* mx, uint8_t* y, float* out_mn,
+                              float* out_mx, int64_t n, hipStream_t stream);
+// lohi: int32[2] scratch that receives min(0, min x) and max(0, max x).
+hipError_t stf_requantization_range(const int32_t* x, const float* mn,
+                                    const float* mx, int32_t* lohi,
+                                    float* out_mn, float* out_mx, int64_t n,
+                                    hipStream_t stream);
+hipError_t stf_quantize_down(const int32_t* x, const float* mn,
+                             const float* mx, int32_t* lohi, uint8_t* y,
+                             float* out_mn, float* out_mx, int64_t n,
+                             hipStream_t stream);
+
 // ---- depthwise.hip ----
 // Filter is [r, s, c, mult]; g->cout is unused.
 hipError_t stf_depthwise_fwd(const void* x, const void* w, void* y,

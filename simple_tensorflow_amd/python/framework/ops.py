@@ -765,6 +765,40 @@ def RegisterShape(op_type):
     return deco
 
 
+def _conv_out_dim(in_dim, k, stride, padding):
+    if in_dim is None or k is None:
+        return None
+    if padding == 'SAME':
+        return (in_dim + stride - 1) // stride
+    return (in_dim - k) // stride + 1
+
+
+# The quantized ops return (tensor, min, max): the two ranges are scalars.
+@RegisterShape('QuantizedConv2D')
+def _quantized_conv2d_shape(op):
+    x, w = op.inputs[0]._shape, op.inputs[1]._shape
+    if x is None or w is None:
+        return [None, (), ()]
+    strides = op.get_attr('strides')
+    padding = op.get_attr('padding')
+    if isinstance(padding, bytes):
+        padding = padding.decode()
+    n, h, wd, _ = x
+    r, s, _, k = w
+    return [(n, _conv_out_dim(h, r, strides[1], padding),
+             _conv_out_dim(wd, s, strides[2], padding), k), (), ()]
+
+
+@RegisterShape('QuantizedMatMul')
+def _quantized_matmul_shape(op):
+    a, b = op.inputs[0]._shape, op.inputs[1]._shape
+    if a is None or b is None:
+        return [None, (), ()]
+    m = a[1] if op.get_attr('transpose_a') else a[0]
+    n = b[0] if op.get_attr('transpose_b') else b[1]
+    return [(m, n), (), ()]
+
+
 def _infer_shapes(op):
     fn = _shape_fns.get(op.type)
     if fn is None:

@@ -1,5 +1,6 @@
 """Quantized ops (reference array_ops quantize section; kernels in
-csrc/kernels/cpu_quantized.cc — quint8/qint32 carried as uint8/int32)."""
+csrc/kernels/cpu_quantized.cc and, on the GPU, csrc/kernels/gpu_quantized.cc
+— quint8/qint32 carried as uint8/int32)."""
 from simple_tensorflow_amd.python.framework import dtypes
 from simple_tensorflow_amd.python.framework.ops import (
     NoGradient, apply_op, convert_to_tensor)
@@ -29,6 +30,18 @@ def quantized_matmul(a, b, min_a, max_a, min_b, max_b, transpose_a=False,
                     transpose_b=transpose_b, name=name)
 
 
+def quantized_conv2d(input, filter, min_input, max_input,  # noqa: A002
+                     min_filter, max_filter, strides, padding, name=None):
+    """NHWC quint8 input, [R,S,C,K] quint8 filter -> (qint32 output,
+    min_output, max_output). strides = [1, sh, sw, 1]."""
+    return apply_op('QuantizedConv2D', input, filter,
+                    convert_to_tensor(min_input),
+                    convert_to_tensor(max_input),
+                    convert_to_tensor(min_filter),
+                    convert_to_tensor(max_filter), strides=list(strides),
+                    padding=padding, name=name)
+
+
 def quantized_relu(features, min_features, max_features, name=None):
     return apply_op('QuantizedRelu', features,
                     convert_to_tensor(min_features),
@@ -49,5 +62,6 @@ def requantization_range(input, input_min, input_max, name=None):  # noqa: A002
 
 
 for _op in ('QuantizeV2', 'Dequantize', 'QuantizedMatMul', 'QuantizedRelu',
+            'QuantizedConv2D',
             'QuantizeDownAndShrinkRange', 'RequantizationRange'):
     NoGradient(_op)

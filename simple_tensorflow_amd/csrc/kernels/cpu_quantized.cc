@@ -2,6 +2,10 @@
 // dequantize_op.cc, quantized_matmul_op.cc, quantization_utils.h):
 // MIN_COMBINED affine mapping float <-> quint8 (carried as uint8), qint32
 // accumulation for the quantized matmul with exact range propagation.
+// Requantize, QuantizedBiasAdd, QuantizedMaxPool and QuantizedReshape carry
+// a quantize_nodes graph (python/tools/quantize_graph_lib.py) from the conv
+// or matmul to the next one. These kernels are the specification that
+// kernels/hip/quantized.hip reproduces bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -9,6 +13,7 @@
 #include <vector>
 
 #include "framework/op_kernel.h"
+#include "kernels/kernel_util.h"
 #include "kernels/quantized_util.h"
 
 namespace stf {
@@ -272,6 +277,187 @@ class QuantizeDownAndShrinkRangeOp : public OpKernel {
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizeDownAndShrinkRange").Device(DEVICE_CPU),
                         QuantizeDownAndShrinkRangeOp);
+
+// QuantizeDownAndShrinkRange's second loop with a range that is given
+// instead of measured: one pass, no reduction.
+class RequantizeOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    float mn = ctx->input(1).flat<float>()[0];
+    float mx = ctx->input(2).flat<float>()[0];
+    double unit = ((double)mx - mn) / 4294967295.0;
+    double lo = (double)ctx->input(3).flat<float>()[0];
+    double hi = (double)ctx->input(4).flat<float>()[0];
+    if (hi <= lo) hi = lo + 1e-6;
+    const int32_t* p = in.flat<int32_t>();
+    int64_t n = in.NumElements();
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    uint8_t* o = out->flat<uint8_t>();
+    double scale = 255.0 / (hi - lo);
+    for (int64_t i = 0; i < n; ++i) {
+      double v = (p[i] * unit - lo) * scale;
+      o[i] = (uint8_t)std::min(255.0, std::max(0.0, std::round(v)));
+    }
+    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = (float)lo;
+    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = (float)hi;
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("Requantize").Device(DEVICE_CPU), RequantizeOp);
+
+// out = round((fx + fb) / unit) with fx, fb the f32 values Dequantize gives
+// and unit the qint32 unit of the output range. That range is +-2^17 times
+// the largest absolute input range value (the reference's headroom rule), so
+// |quotient| stays near 2^15 and nothing clamps.
+class QuantizedBiasAddOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    const Tensor& bias = ctx->input(1);
+    OP_REQUIRES(ctx, in.dims() >= 1 && bias.dims() == 1 &&
+                         in.dim_size(in.dims() - 1) == bias.dim_size(0),
+                errors::InvalidArgument("QuantizedBiasAdd: the last input "
+                                        "dimension must equal the bias "
+                                        "length"));
+    float min_x = ctx->input(2).flat<float>()[0];
+    float max_x = ctx->input(3).flat<float>()[0];
+    float min_b = ctx->input(4).flat<float>()[0];
+    float max_b = ctx->input(5).flat<float>()[0];
+    float max_out = QuantBiasAddMax(min_x, max_x, min_b, max_b);
+    float min_out = -max_out;
+    double unit = ((double)max_out - min_out) / 4294967295.0;
+    float sx = QuantStep(min_x, max_x);
+    float sb = QuantStep(min_b, max_b);
+    int64_t C = bias.dim_size(0);
+    int64_t n = in.NumElements();
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    const uint8_t* x = in.flat<uint8_t>();
+    const uint8_t* b = bias.flat<uint8_t>();
+    int32_t* o = out->flat<int32_t>();
+    for (int64_t i = 0; i < n; ++i) {
+      float fx = min_x + (float)x[i] * sx;
+      float fb = min_b + (float)b[i % C] * sb;
+      o[i] = unit == 0
+                 ? 0
+                 : (int32_t)std::round(((double)fx + (double)fb) / unit);
+    }
+    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = min_out;
+    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = max_out;
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedBiasAdd").Device(DEVICE_CPU),
+                        QuantizedBiasAddOp);
+
+// NHWC max over the taps inside the image; geometry as GetPoolParams of
+// cpu_nn.cc. The mapping is monotone, so the ranges pass through.
+class QuantizedMaxPoolOp : public OpKernel {
+ public:
+  explicit QuantizedMaxPoolOp(OpKernelConstruction* c) : OpKernel(c) {
+    c->GetAttr("ksize", &ksize_);
+    c->GetAttr("strides", &strides_);
+    c->GetAttr("padding", &padding_);
+  }
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    OP_REQUIRES(ctx, in.dims() == 4,
+                errors::InvalidArgument("QuantizedMaxPool needs rank-4 "
+                                        "input"));
+    OP_REQUIRES(ctx, ksize_.size() == 4 && strides_.size() == 4 &&
+                         ksize_[1] >= 1 && ksize_[2] >= 1 &&
+                         strides_[1] >= 1 && strides_[2] >= 1,
+                errors::InvalidArgument("QuantizedMaxPool ksize and strides "
+                                        "must be [1, h, w, 1]"));
+    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
+                errors::InvalidArgument("QuantizedMaxPool padding must be "
+                                        "SAME or VALID"));
+    int64_t N = in.dim_size(0), H = in.dim_size(1), W = in.dim_size(2),
+            C = in.dim_size(3);
+    int64_t kh = ksize_[1], kw = ksize_[2], sh = strides_[1],
+            sw = strides_[2], P, Q, pad_h = 0, pad_w = 0;
+    if (padding_ == "SAME") {
+      P = (H + sh - 1) / sh;
+      Q = (W + sw - 1) / sw;
+      pad_h = std::max<int64_t>(0, (P - 1) * sh + kh - H) / 2;
+      pad_w = std::max<int64_t>(0, (Q - 1) * sw + kw - W) / 2;
+    } else {
+      P = (H - kh) / sh + 1;
+      Q = (W - kw) / sw + 1;
+    }
+    OP_REQUIRES(ctx, P >= 0 && Q >= 0,
+                errors::InvalidArgument("QuantizedMaxPool window larger "
+                                        "than the VALID input"));
+    Tensor* out = ctx->allocate_output(0, TensorShape({N, P, Q, C}));
+    const uint8_t* x = in.flat<uint8_t>();
+    uint8_t* y = out->flat<uint8_t>();
+    for (int64_t n = 0; n < N; ++n)
+      for (int64_t p = 0; p < P; ++p)
+        for (int64_t q = 0; q < Q; ++q) {
+          uint8_t* o = y + ((n * P + p) * Q + q) * C;
+          std::fill(o, o + C, (uint8_t)0);
+          for (int64_t r = 0; r < kh; ++r) {
+            int64_t ih = p * sh - pad_h + r;
+            if (ih < 0 || ih >= H) continue;
+            for (int64_t s = 0; s < kw; ++s) {
+              int64_t iw = q * sw - pad_w + s;
+              if (iw < 0 || iw >= W) continue;
+              const uint8_t* xr = x + ((n * H + ih) * W + iw) * C;
+              for (int64_t c = 0; c < C; ++c) o[c] = std::max(o[c], xr[c]);
+            }
+          }
+        }
+    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
+        ctx->input(1).flat<float>()[0];
+    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
+        ctx->input(2).flat<float>()[0];
+  }
+
+ private:
+  std::vector<int64_t> ksize_, strides_;
+  std::string padding_;
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedMaxPool").Device(DEVICE_CPU),
+                        QuantizedMaxPoolOp);
+
+// Reshape with the two range scalars forwarded. Like ReshapeOp it shares
+// the buffers and touches no tensor data, so one class serves both devices.
+class QuantizedReshapeOp : public OpKernel {
+ public:
+  explicit QuantizedReshapeOp(OpKernelConstruction* c) : OpKernel(c) {
+    set_expensive(false);
+  }
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    auto dims = IntVector(ctx->input(1));
+    int64_t known = 1;
+    int infer = -1;
+    for (size_t i = 0; i < dims.size(); ++i) {
+      if (dims[i] == -1) {
+        OP_REQUIRES(ctx, infer < 0,
+                    errors::InvalidArgument("multiple -1 dims in "
+                                            "QuantizedReshape"));
+        infer = (int)i;
+      } else {
+        known *= dims[i];
+      }
+    }
+    if (infer >= 0) dims[infer] = known ? in.NumElements() / known : 0;
+    TensorShape shape(dims);
+    OP_REQUIRES(ctx, shape.num_elements() == in.NumElements(),
+                errors::InvalidArgument("QuantizedReshape size mismatch: "
+                                        "input ", in.shape().DebugString(),
+                                        " to ", shape.DebugString()));
+    ctx->set_output(0, in.Reshaped(shape));
+    ctx->set_output(1, ctx->input(2));
+    ctx->set_output(2, ctx->input(3));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedReshape").Device(DEVICE_CPU),
+                        QuantizedReshapeOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedReshape").Device(DEVICE_GPU).HostMemory("shape"),
+    QuantizedReshapeOp);
 
 }  // namespace
 }  // namespace stf

@@ -1,6 +1,7 @@
 // GPU OpKernels: the quantized family (QuantizeV2, Dequantize,
 // QuantizedMatMul, QuantizedConv2D, QuantizedRelu, RequantizationRange,
-// QuantizeDownAndShrinkRange) on kernels/hip/gemm_i8.hip and
+// QuantizeDownAndShrinkRange, Requantize, QuantizedBiasAdd,
+// QuantizedMaxPool) on kernels/hip/gemm_i8.hip and
 // kernels/hip/quantized.hip.
 //
 // The min/max ranges live in device memory on both sides of every op: no
@@ -248,6 +249,114 @@ class GpuQuantizeDownAndShrinkRangeOp : public OpKernel {
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizeDownAndShrinkRange").Device(DEVICE_GPU),
                         GpuQuantizeDownAndShrinkRangeOp);
+
+class GpuRequantizeOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    OP_HIP_OK(ctx, stf_requantize((const int32_t*)in.raw_data(),
+                                  F32(ctx->input(1)), F32(ctx->input(2)),
+                                  F32(ctx->input(3)), F32(ctx->input(4)),
+                                  (uint8_t*)out->raw_data(), omn, omx,
+                                  in.NumElements(), GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("Requantize").Device(DEVICE_GPU),
+                        GpuRequantizeOp);
+
+class GpuQuantizedBiasAddOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    const Tensor& bias = ctx->input(1);
+    OP_REQUIRES(ctx, in.dims() >= 1 && bias.dims() == 1 &&
+                         in.dim_size(in.dims() - 1) == bias.dim_size(0),
+                errors::InvalidArgument("QuantizedBiasAdd: the last input "
+                                        "dimension must equal the bias "
+                                        "length"));
+    int64_t C = bias.dim_size(0);
+    int64_t rows = C ? in.NumElements() / C : 0;
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    OP_HIP_OK(ctx, stf_quantized_bias_add(
+                       (const uint8_t*)in.raw_data(),
+                       (const uint8_t*)bias.raw_data(), F32(ctx->input(2)),
+                       F32(ctx->input(3)), F32(ctx->input(4)),
+                       F32(ctx->input(5)), (int32_t*)out->raw_data(), omn,
+                       omx, rows, C, GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedBiasAdd").Device(DEVICE_GPU),
+                        GpuQuantizedBiasAddOp);
+
+class GpuQuantizedMaxPoolOp : public OpKernel {
+ public:
+  explicit GpuQuantizedMaxPoolOp(OpKernelConstruction* c) : OpKernel(c) {
+    c->GetAttr("ksize", &ksize_);
+    c->GetAttr("strides", &strides_);
+    c->GetAttr("padding", &padding_);
+  }
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& x = ctx->input(0);
+    OP_REQUIRES(ctx, x.dims() == 4,
+                errors::InvalidArgument("QuantizedMaxPool needs rank-4 "
+                                        "input"));
+    OP_REQUIRES(ctx, ksize_.size() == 4 && strides_.size() == 4 &&
+                         ksize_[1] >= 1 && ksize_[2] >= 1 &&
+                         strides_[1] >= 1 && strides_[2] >= 1,
+                errors::InvalidArgument("QuantizedMaxPool ksize and strides "
+                                        "must be [1, h, w, 1]"));
+    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
+                errors::InvalidArgument("QuantizedMaxPool padding must be "
+                                        "SAME or VALID"));
+    StfPoolGeom g;
+    g.N = (int)x.dim_size(0);
+    g.H = (int)x.dim_size(1);
+    g.W = (int)x.dim_size(2);
+    g.C = (int)x.dim_size(3);
+    g.kh = (int)ksize_[1];
+    g.kw = (int)ksize_[2];
+    g.sh = (int)strides_[1];
+    g.sw = (int)strides_[2];
+    if (padding_ == "SAME") {
+      g.P = (g.H + g.sh - 1) / g.sh;
+      g.Q = (g.W + g.sw - 1) / g.sw;
+      g.ph = std::max(0, (g.P - 1) * g.sh + g.kh - g.H) / 2;
+      g.pw = std::max(0, (g.Q - 1) * g.sw + g.kw - g.W) / 2;
+    } else {
+      g.P = (g.H - g.kh) / g.sh + 1;
+      g.Q = (g.W - g.kw) / g.sw + 1;
+      g.ph = g.pw = 0;
+    }
+    OP_REQUIRES(ctx, g.P >= 0 && g.Q >= 0,
+                errors::InvalidArgument("QuantizedMaxPool window larger "
+                                        "than the VALID input"));
+    Tensor* y = ctx->allocate_output(
+        0, TensorShape({(int64_t)g.N, (int64_t)g.P, (int64_t)g.Q,
+                        (int64_t)g.C}));
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    OP_HIP_OK(ctx, stf_quantized_max_pool(
+                       (const uint8_t*)x.raw_data(), F32(ctx->input(1)),
+                       F32(ctx->input(2)), (uint8_t*)y->raw_data(), omn, omx,
+                       &g, GPU_STREAM(ctx)));
+  }
+
+ private:
+  std::vector<int64_t> ksize_, strides_;
+  std::string padding_;
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedMaxPool").Device(DEVICE_GPU),
+                        GpuQuantizedMaxPoolOp);
+
+// QuantizedReshape moves no data: its one kernel class is registered for
+// both devices in kernels/cpu_quantized.cc, as Reshape's is in cpu_basic.cc.
 
 }  // namespace
 }  // namespace stf

@@ -1,5 +1,6 @@
 // Elementwise and range kernels of the quantized ops: QuantizeV2,
-// Dequantize, QuantizedRelu, RequantizationRange, QuantizeDownAndShrinkRange.
+// Dequantize, QuantizedRelu, RequantizationRange, QuantizeDownAndShrinkRange,
+// Requantize, QuantizedBiasAdd, QuantizedMaxPool.
 //
 // Every output is bit-equal to kernels/cpu_quantized.cc: the same IEEE
 // operations in the same order and precision (f32 for the quint8 paths, f64
@@ -243,6 +244,225 @@ __global__ void QuantizeDownKernel(const int32_t* __restrict__ x,
     y[i] = QuantizeDownOne(x[i], unit, lo, scale);
 }
 
+__device__ __forceinline__ uint32_t QuantizeDownFour(int4 v, double unit,
+                                                     double lo,
+                                                     double scale) {
+  return (uint32_t)QuantizeDownOne(v.x, unit, lo, scale) |
+         (uint32_t)QuantizeDownOne(v.y, unit, lo, scale) << 8 |
+         (uint32_t)QuantizeDownOne(v.z, unit, lo, scale) << 16 |
+         (uint32_t)QuantizeDownOne(v.w, unit, lo, scale) << 24;
+}
+
+// QuantizeDownKernel with the range given: no reduction in front of it. A
+// thread takes 16 consecutive elements, four 16-byte loads and one 16-byte
+// store.
+__global__ void RequantizeKernel(const int32_t* __restrict__ x,
+                                 const float* __restrict__ mnp,
+                                 const float* __restrict__ mxp,
+                                 const float* __restrict__ req_mn,
+                                 const float* __restrict__ req_mx,
+                                 uint8_t* __restrict__ y,
+                                 float* __restrict__ out_mn,
+                                 float* __restrict__ out_mx, int64_t n) {
+  double unit = ((double)mxp[0] - mnp[0]) / 4294967295.0;
+  double lo = (double)req_mn[0], hi = (double)req_mx[0];
+  if (hi <= lo) hi = lo + 1e-6;
+  double scale = 255.0 / (hi - lo);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = (float)lo;
+    out_mx[0] = (float)hi;
+  }
+  int64_t n16 = n / 16;
+  for (int64_t i = tid; i < n16; i += stride) {
+    const int4* src = (const int4*)x + i * 4;
+    int4 a = src[0], b = src[1], c = src[2], d = src[3];
+    uint4 o;
+    o.x = QuantizeDownFour(a, unit, lo, scale);
+    o.y = QuantizeDownFour(b, unit, lo, scale);
+    o.z = QuantizeDownFour(c, unit, lo, scale);
+    o.w = QuantizeDownFour(d, unit, lo, scale);
+    ((uint4*)y)[i] = o;
+  }
+  for (int64_t i = n16 * 16 + tid; i < n; i += stride)
+    y[i] = QuantizeDownOne(x[i], unit, lo, scale);
+}
+
+// The range of a QuantizedBiasAdd result and the qint32 unit of that range.
+struct BiasAddScale {
+  float min_x, step_x, min_b, step_b, max_out;
+  double unit;
+};
+
+__device__ __forceinline__ BiasAddScale MakeBiasAddScale(
+    const float* min_x, const float* max_x, const float* min_b,
+    const float* max_b) {
+  BiasAddScale s;
+  s.min_x = min_x[0];
+  s.min_b = min_b[0];
+  s.step_x = stf::QuantStep(s.min_x, max_x[0]);
+  s.step_b = stf::QuantStep(s.min_b, max_b[0]);
+  s.max_out = stf::QuantBiasAddMax(s.min_x, max_x[0], s.min_b, max_b[0]);
+  float min_out = -s.max_out;
+  s.unit = ((double)s.max_out - min_out) / 4294967295.0;
+  return s;
+}
+
+// The f64 divide is the CPU kernel's: a reciprocal multiply rounds
+// differently.
+__device__ __forceinline__ int32_t BiasAddOne(uint32_t x, uint32_t b,
+                                              const BiasAddScale& s) {
+  float fx = s.min_x + (float)x * s.step_x;
+  float fb = s.min_b + (float)b * s.step_b;
+  if (s.unit == 0) return 0;
+  return (int32_t)round(((double)fx + (double)fb) / s.unit);
+}
+
+// x viewed as [rows, C]. VEC: C % 4 == 0 and a thread takes 4 consecutive
+// channels (n4 = rows * C / 4 groups); otherwise one element per thread.
+template <bool VEC>
+__global__ void QuantizedBiasAddKernel(const uint8_t* __restrict__ x,
+                                       const uint8_t* __restrict__ bias,
+                                       const float* __restrict__ min_x,
+                                       const float* __restrict__ max_x,
+                                       const float* __restrict__ min_b,
+                                       const float* __restrict__ max_b,
+                                       int32_t* __restrict__ y,
+                                       float* __restrict__ out_mn,
+                                       float* __restrict__ out_mx,
+                                       int64_t total, int64_t C) {
+  BiasAddScale s = MakeBiasAddScale(min_x, max_x, min_b, max_b);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = -s.max_out;
+    out_mx[0] = s.max_out;
+  }
+  if (VEC) {
+    int64_t c4 = C / 4;
+    for (int64_t i = tid; i < total; i += stride) {
+      uint32_t xv = ((const uint32_t*)x)[i];
+      uint32_t bv = ((const uint32_t*)bias)[i % c4];
+      int4 o;
+      o.x = BiasAddOne(xv & 0xff, bv & 0xff, s);
+      o.y = BiasAddOne((xv >> 8) & 0xff, (bv >> 8) & 0xff, s);
+      o.z = BiasAddOne((xv >> 16) & 0xff, (bv >> 16) & 0xff, s);
+      o.w = BiasAddOne(xv >> 24, bv >> 24, s);
+      ((int4*)y)[i] = o;
+    }
+  } else {
+    for (int64_t i = tid; i < total; i += stride)
+      y[i] = BiasAddOne(x[i], bias[i % C], s);
+  }
+}
+
+using u16x2 = __attribute__((ext_vector_type(2))) unsigned short;
+
+// max of the two u16 halves of a word
+__device__ __forceinline__ uint32_t PkMaxU16(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(
+      uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a),
+                                          __builtin_bit_cast(u16x2, b)));
+}
+
+// Byte-wise running maximum of 4 u8 lanes, kept as the even and the odd
+// bytes widened to u16 pairs so that each tap costs two packed maxima.
+struct MaxU8x4Acc {
+  uint32_t even = 0, odd = 0;
+  __device__ __forceinline__ void Take(uint32_t w) {
+    even = PkMaxU16(even, w & 0x00ff00ffu);
+    odd = PkMaxU16(odd, (w >> 8) & 0x00ff00ffu);
+  }
+  __device__ __forceinline__ uint32_t Word() const {
+    return even | odd << 8;
+  }
+};
+
+__device__ __forceinline__ void PoolWindow(const StfPoolGeom& g, int p, int q,
+                                           int* h0, int* h1, int* w0,
+                                           int* w1) {
+  *h0 = max(p * g.sh - g.ph, 0);
+  *h1 = min(p * g.sh - g.ph + g.kh, g.H);
+  *w0 = max(q * g.sw - g.pw, 0);
+  *w1 = min(q * g.sw - g.pw + g.kw, g.W);
+}
+
+// C % 16 == 0: a thread owns 16 channels of one output pixel. The window is
+// clipped to the image, so every tap that is read lies inside it.
+__global__ void QuantizedMaxPoolV16Kernel(const uint8_t* __restrict__ x,
+                                          const float* __restrict__ mnp,
+                                          const float* __restrict__ mxp,
+                                          uint8_t* __restrict__ y,
+                                          float* __restrict__ out_mn,
+                                          float* __restrict__ out_mx,
+                                          StfPoolGeom g, int64_t total16) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = mnp[0];
+    out_mx[0] = mxp[0];
+  }
+  int64_t c16 = g.C / 16;
+  for (int64_t i = tid; i < total16; i += stride) {
+    int64_t rem = i;
+    int64_t cw = rem % c16; rem /= c16;
+    int q = (int)(rem % g.Q); rem /= g.Q;
+    int p = (int)(rem % g.P); rem /= g.P;
+    int64_t n = rem;
+    int h0, h1, w0, w1;
+    PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
+    MaxU8x4Acc a0, a1, a2, a3;
+    for (int ih = h0; ih < h1; ++ih)
+      for (int iw = w0; iw < w1; ++iw) {
+        uint4 v = *(const uint4*)(x + ((n * g.H + ih) * g.W + iw) * g.C +
+                                  cw * 16);
+        a0.Take(v.x);
+        a1.Take(v.y);
+        a2.Take(v.z);
+        a3.Take(v.w);
+      }
+    uint4 o;
+    o.x = a0.Word();
+    o.y = a1.Word();
+    o.z = a2.Word();
+    o.w = a3.Word();
+    // ((n * P + p) * Q + q) * C + cw * 16 == i * 16
+    ((uint4*)y)[i] = o;
+  }
+}
+
+__global__ void QuantizedMaxPoolKernel(const uint8_t* __restrict__ x,
+                                       const float* __restrict__ mnp,
+                                       const float* __restrict__ mxp,
+                                       uint8_t* __restrict__ y,
+                                       float* __restrict__ out_mn,
+                                       float* __restrict__ out_mx,
+                                       StfPoolGeom g, int64_t total) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = mnp[0];
+    out_mx[0] = mxp[0];
+  }
+  for (int64_t i = tid; i < total; i += stride) {
+    int64_t rem = i;
+    int64_t c = rem % g.C; rem /= g.C;
+    int q = (int)(rem % g.Q); rem /= g.Q;
+    int p = (int)(rem % g.P); rem /= g.P;
+    int64_t n = rem;
+    int h0, h1, w0, w1;
+    PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
+    uint32_t best = 0;
+    for (int ih = h0; ih < h1; ++ih)
+      for (int iw = w0; iw < w1; ++iw) {
+        uint32_t v = x[((n * g.H + ih) * g.W + iw) * g.C + c];
+        best = best < v ? v : best;
+      }
+    y[i] = (uint8_t)best;
+  }
+}
+
 hipError_t MinMaxI32(const int32_t* x, int32_t* lohi, int64_t n,
                      hipStream_t stream) {
   hipError_t e = hipMemsetAsync(lohi, 0, 2 * sizeof(int32_t), stream);
@@ -306,5 +526,54 @@ extern "C" hipError_t stf_quantize_down(const int32_t* x, const float* mn,
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(QuantizeDownKernel, ElemwiseGrid(n), dim3(256), 0,
                      stream, x, lohi, mn, mx, y, out_mn, out_mx, n);
+  return hipGetLastError();
+}
+
+// The three entries below launch for an empty tensor too: thread 0 writes
+// the output ranges.
+extern "C" hipError_t stf_requantize(const int32_t* x, const float* mn,
+                                     const float* mx, const float* req_mn,
+                                     const float* req_mx, uint8_t* y,
+                                     float* out_mn, float* out_mx, int64_t n,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(RequantizeKernel, ElemwiseGrid(n, 256, 16), dim3(256), 0,
+                     stream, x, mn, mx, req_mn, req_mx, y, out_mn, out_mx, n);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantized_bias_add(
+    const uint8_t* x, const uint8_t* bias, const float* min_x,
+    const float* max_x, const float* min_b, const float* max_b, int32_t* y,
+    float* out_mn, float* out_mx, int64_t rows, int64_t C,
+    hipStream_t stream) {
+  int64_t n = rows * C;
+  if (C > 0 && C % 4 == 0)
+    hipLaunchKernelGGL(QuantizedBiasAddKernel<true>,
+                       ElemwiseGrid(n / 4, 256, 1),
+                       dim3(256), 0, stream, x, bias, min_x, max_x, min_b,
+                       max_b, y, out_mn, out_mx, n / 4, C);
+  else
+    hipLaunchKernelGGL(QuantizedBiasAddKernel<false>, ElemwiseGrid(n),
+                       dim3(256), 0, stream, x, bias, min_x, max_x, min_b,
+                       max_b, y, out_mn, out_mx, n, C);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantized_max_pool(const uint8_t* x,
+                                             const float* mn, const float* mx,
+                                             uint8_t* y, float* out_mn,
+                                             float* out_mx,
+                                             const StfPoolGeom* gp,
+                                             hipStream_t stream) {
+  const StfPoolGeom g = *gp;
+  int64_t total = (int64_t)g.N * g.P * g.Q * g.C;
+  if (g.C > 0 && g.C % 16 == 0)
+    hipLaunchKernelGGL(QuantizedMaxPoolV16Kernel,
+                       ElemwiseGrid(total / 16, 256, 1), dim3(256), 0,
+                       stream, x, mn, mx, y, out_mn, out_mx, g, total / 16);
+  else
+    hipLaunchKernelGGL(QuantizedMaxPoolKernel, ElemwiseGrid(total, 256, 1),
+                       dim3(256), 0, stream, x, mn, mx, y, out_mn, out_mx, g,
+                       total);
   return hipGetLastError();
 }

@@ -172,6 +172,23 @@ hipError_t stf_quantize_down(const int32_t* x, const float* mn,
                              const float* mx, int32_t* lohi, uint8_t* y,
                              float* out_mn, float* out_mx, int64_t n,
                              hipStream_t stream);
+// stf_quantize_down's second pass with the range [req_mn, req_mx] given.
+hipError_t stf_requantize(const int32_t* x, const float* mn, const float* mx,
+                          const float* req_mn, const float* req_mx,
+                          uint8_t* y, float* out_mn, float* out_mx, int64_t n,
+                          hipStream_t stream);
+// x: quint8 [rows, C], bias: quint8 [C] -> y: qint32 [rows, C].
+hipError_t stf_quantized_bias_add(const uint8_t* x, const uint8_t* bias,
+                                  const float* min_x, const float* max_x,
+                                  const float* min_b, const float* max_b,
+                                  int32_t* y, float* out_mn, float* out_mx,
+                                  int64_t rows, int64_t C,
+                                  hipStream_t stream);
+// NHWC quint8 max over the in-image taps; the range is copied through.
+hipError_t stf_quantized_max_pool(const uint8_t* x, const float* mn,
+                                  const float* mx, uint8_t* y, float* out_mn,
+                                  float* out_mx, const StfPoolGeom* g,
+                                  hipStream_t stream);
 
 // ---- depthwise.hip ----
 // Filter is [r, s, c, mult]; g->cout is unused.

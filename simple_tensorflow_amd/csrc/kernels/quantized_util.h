@@ -34,4 +34,18 @@ STF_QHD float QuantProductMax(float step_a, float step_b) {
   return (float)(2147483647.0 * (step_a * step_b));
 }
 
+// Upper end of QuantizedBiasAdd's symmetric qint32 output range: 2^17 times
+// the largest absolute value among the two input ranges.
+STF_QHD float QuantBiasAddMax(float min_x, float max_x, float min_b,
+                              float max_b) {
+  float m = fabsf(min_x);
+  float a = fabsf(max_x);
+  m = m < a ? a : m;
+  a = fabsf(min_b);
+  m = m < a ? a : m;
+  a = fabsf(max_b);
+  m = m < a ? a : m;
+  return m * 131072.f;
+}
+
 }  // namespace stf

@@ -799,6 +799,49 @@ def _quantized_matmul_shape(op):
     return [(m, n), (), ()]
 
 
+@RegisterShape('Requantize')
+@RegisterShape('QuantizedBiasAdd')
+def _quantized_same_shape(op):
+    return [op.inputs[0]._shape, (), ()]
+
+
+@RegisterShape('QuantizedMaxPool')
+def _quantized_max_pool_shape(op):
+    x = op.inputs[0]._shape
+    if x is None:
+        return [None, (), ()]
+    ksize = op.get_attr('ksize')
+    strides = op.get_attr('strides')
+    padding = op.get_attr('padding')
+    if isinstance(padding, bytes):
+        padding = padding.decode()
+    n, h, w, c = x
+    return [(n, _conv_out_dim(h, ksize[1], strides[1], padding),
+             _conv_out_dim(w, ksize[2], strides[2], padding), c), (), ()]
+
+
+@RegisterShape('QuantizedReshape')
+def _quantized_reshape_shape(op):
+    x = op.inputs[0]._shape
+    sv = getattr(op.inputs[1], '_const_value', None)
+    if sv is None:
+        return [None, (), ()]
+    dims = [int(d) for d in np.asarray(sv).reshape(-1)]
+    if -1 in dims:
+        known = 1
+        for d in dims:
+            if d != -1:
+                known *= d
+        total = None
+        if x is not None and all(d is not None for d in x):
+            total = 1
+            for d in x:
+                total *= d
+        dims[dims.index(-1)] = (total // known if total is not None and known
+                                else None)
+    return [tuple(dims), (), ()]
+
+
 def _infer_shapes(op):
     fn = _shape_fns.get(op.type)
     if fn is None:

@@ -61,7 +61,44 @@ def requantization_range(input, input_min, input_max, name=None):  # noqa: A002
                     convert_to_tensor(input_max), name=name)
 
 
+def requantize(input, input_min, input_max,  # noqa: A002
+               requested_output_min, requested_output_max, name=None):
+    """qint32 -> (quint8 output, output_min, output_max) over the requested
+    range: QuantizeDownAndShrinkRange without the min/max pass."""
+    return apply_op('Requantize', input, convert_to_tensor(input_min),
+                    convert_to_tensor(input_max),
+                    convert_to_tensor(requested_output_min),
+                    convert_to_tensor(requested_output_max), name=name)
+
+
+def quantized_bias_add(input, bias, min_input, max_input,  # noqa: A002
+                       min_bias, max_bias, name=None):
+    """quint8 [..., C] + quint8 [C] -> (qint32 output, min_out, max_out)."""
+    return apply_op('QuantizedBiasAdd', input, bias,
+                    convert_to_tensor(min_input),
+                    convert_to_tensor(max_input),
+                    convert_to_tensor(min_bias),
+                    convert_to_tensor(max_bias), name=name)
+
+
+def quantized_max_pool(input, min_input, max_input, ksize,  # noqa: A002
+                       strides, padding, name=None):
+    """NHWC quint8 -> (quint8 output, min_output, max_output)."""
+    return apply_op('QuantizedMaxPool', input, convert_to_tensor(min_input),
+                    convert_to_tensor(max_input), ksize=list(ksize),
+                    strides=list(strides), padding=padding, name=name)
+
+
+def quantized_reshape(tensor, shape, input_min, input_max, name=None):
+    return apply_op('QuantizedReshape', tensor,
+                    convert_to_tensor(shape, dtype=dtypes.int32),
+                    convert_to_tensor(input_min),
+                    convert_to_tensor(input_max), name=name)
+
+
 for _op in ('QuantizeV2', 'Dequantize', 'QuantizedMatMul', 'QuantizedRelu',
             'QuantizedConv2D',
-            'QuantizeDownAndShrinkRange', 'RequantizationRange'):
+            'QuantizeDownAndShrinkRange', 'RequantizationRange',
+            'Requantize', 'QuantizedBiasAdd', 'QuantizedMaxPool',
+            'QuantizedReshape'):
     NoGradient(_op)

@@ -1,0 +1,307 @@
+"""quantize_weights and quantize_nodes graph transforms (capability analogs
+of reference tools/graph_transforms/quantize_weights.cc and
+quantize_nodes.cc), over the node dicts of graph_util._as_nodes.
+
+The session's constant folder skips multi-output nodes, so a
+QuantizeV2(Const) would run on every step. Both transforms therefore
+quantize constants here, in numpy, bit for bit as the QuantizeV2 kernel
+does, and emit a uint8 Const with two float scalar Consts for the range.
+
+Constant ranges are nudged so that 0.0 is exactly representable: otherwise
+the rounding of the zero point is a systematic offset on every weight, which
+the all-positive activations behind a ReLU multiply instead of averaging out.
+"""
+import numpy as np
+
+from simple_tensorflow_amd.python.framework import dtypes, graph_util
+from simple_tensorflow_amd.python.tools.optimize_for_inference_lib import (
+    _const_value, _make_const)
+
+_F32 = int(dtypes.float32)
+_U8 = int(dtypes.uint8)
+_I32 = int(dtypes.int32)
+
+
+# ---------------------------------------------------------------------------
+# numpy side of QuantizeV2
+# ---------------------------------------------------------------------------
+def _round_half_away(v):
+    """std::round on an array: np.round is half-to-even."""
+    t = np.trunc(v)
+    frac = v - t  # exact
+    return t + np.where(np.abs(frac) >= 0.5, np.sign(v), 0).astype(v.dtype)
+
+
+def quantize_array(x, mn, mx):
+    """float array -> uint8 exactly as the QuantizeV2 kernel: f32
+    (x - mn) * (255 / (mx - mn)), rounded half away from zero, clamped."""
+    x = np.asarray(x, np.float32)
+    mn, mx = np.float32(mn), np.float32(mx)
+    if mx <= mn:
+        mx = mn + np.float32(1e-6)
+    scale = np.float32(255.0) / (mx - mn)
+    q = _round_half_away((x - mn) * scale)
+    return np.minimum(np.float32(255), np.maximum(np.float32(0), q)) \
+        .astype(np.uint8)
+
+
+def nudged_range(mn, mx):
+    """Widens [mn, mx] to include 0 and shifts it so that 0.0 falls exactly
+    on a quantized value z: returns f32 (-z * step, (255 - z) * step)."""
+    mn = min(float(mn), 0.0)
+    mx = max(float(mx), 0.0)
+    if mx == mn:
+        mx = 1.0
+    step = (mx - mn) / 255.0
+    z = np.floor(-mn / step + 0.5)
+    return np.float32(-z * step), np.float32((255.0 - z) * step)
+
+
+def _quantized_const_nodes(name, value):
+    """name/quint8_const, name/min, name/max for a float array."""
+    mn, mx = nudged_range(value.min(), value.max()) if value.size else \
+        nudged_range(0.0, 0.0)
+    return [_make_const(name + '/quint8_const',
+                        quantize_array(value, mn, mx), _U8),
+            _make_const(name + '/min', np.array(mn, np.float32), _F32),
+            _make_const(name + '/max', np.array(mx, np.float32), _F32)]
+
+
+def _is_float_const(node):
+    return node['op'] == 'Const' and node['attr']['dtype'][1] == _F32
+
+
+def _node(name, op, inputs, attr, device=''):
+    return {'name': name, 'op': op, 'input': list(inputs), 'device': device,
+            'attr': attr}
+
+
+def _dequantize(name, src, device=''):
+    return _node(name, 'Dequantize', [src + ':0', src + ':1', src + ':2'],
+                 {'T': ('type', _U8), 'mode': ('s', b'MIN_COMBINED')},
+                 device)
+
+
+# ---------------------------------------------------------------------------
+# quantize_weights
+# ---------------------------------------------------------------------------
+def quantize_weights(graph_def, minimum_size=1024):
+    """Stores every float Const of at least minimum_size elements in 8 bit:
+    name/quint8_const, name/min and name/max feed a Dequantize that carries
+    the original name, so consumers are untouched and the graph stays
+    float."""
+    out = []
+    for n in graph_util._as_nodes(graph_def):
+        value = _const_value(n) if _is_float_const(n) else None
+        if value is None or value.size < minimum_size:
+            out.append(n)
+            continue
+        parts = _quantized_const_nodes(n['name'], value)
+        out.extend(parts)
+        out.append(_node(n['name'], 'Dequantize', [p['name'] for p in parts],
+                         {'T': ('type', _U8),
+                          'mode': ('s', b'MIN_COMBINED')},
+                         n.get('device', '')))
+    return graph_util._serialize(out)
+
+
+# ---------------------------------------------------------------------------
+# quantize_nodes
+# ---------------------------------------------------------------------------
+def _attr(node, key, default=None):
+    av = node['attr'].get(key)
+    return default if av is None else av[1]
+
+
+def _str_attr(node, key, default):
+    v = _attr(node, key, default)
+    return v.decode() if isinstance(v, bytes) else v
+
+
+def _is_f32(node):
+    return _attr(node, 'T', _F32) == _F32
+
+
+def _window_ok(v):
+    return v is not None and len(v['i']) == 4 and v['i'][0] == 1 and \
+        v['i'][3] == 1
+
+
+def _conv_ok(n):
+    return _str_attr(n, 'data_format', 'NHWC') == 'NHWC' and \
+        _str_attr(n, 'padding', '') in ('SAME', 'VALID') and \
+        _window_ok(_attr(n, 'strides'))
+
+
+def _pool_ok(n):
+    return _conv_ok(n) and _window_ok(_attr(n, 'ksize'))
+
+
+def _nhwc(n):
+    return _str_attr(n, 'data_format', 'NHWC') == 'NHWC'
+
+
+# op -> (quantized op, indices of the inputs to quantize, int32 result,
+#        can the quantized op express this node?, attributes carried over)
+_REWRITES = {
+    'Conv2D': ('QuantizedConv2D', (0, 1), True, _conv_ok,
+               ('strides', 'padding')),
+    'MatMul': ('QuantizedMatMul', (0, 1), True, lambda n: True,
+               ('transpose_a', 'transpose_b')),
+    'BiasAdd': ('QuantizedBiasAdd', (0, 1), True, _nhwc, ()),
+    'Relu': ('QuantizedRelu', (0,), False, lambda n: True, ()),
+    'MaxPool': ('QuantizedMaxPool', (0,), False, _pool_ok,
+                ('ksize', 'strides', 'padding')),
+    'Reshape': ('QuantizedReshape', (0,), False,
+                lambda n: _attr(n, 'Tshape', _I32) == _I32, ()),
+}
+
+
+def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
+                   fallback_max=None):
+    """Rewrites float32 Conv2D, MatMul, BiasAdd, Relu, MaxPool and Reshape
+    (NHWC) to their quantized ops.
+
+    First pass: every such node, in isolation, becomes quantized inputs
+    (activations through Reshape/Min/Max/QuantizeV2, Consts through numpy),
+    the quantized op, RequantizationRange + Requantize behind an int32
+    result, and a Dequantize that carries the original name. Second pass:
+    a first-pass Dequantize that feeds nothing but first-pass quantize
+    groups is removed together with those groups, and their consumers read
+    the uint8 tensor and its two range scalars directly.
+
+    With fallback_min and fallback_max every RequantizationRange is replaced
+    by the two constants, which leaves no reduction behind the input."""
+    if (fallback_min is None) != (fallback_max is None):
+        raise ValueError('quantize_nodes needs both fallback_min and '
+                         'fallback_max, or neither')
+    nodes = graph_util._as_nodes(graph_def)
+    by_name = {n['name']: n for n in nodes}
+    protected = set(inputs) | set(outputs)
+
+    out = []
+    const_done = set()
+    groups = []      # quantize groups: {'source', 'names', 'out'}
+    dequantized = {}  # original name -> name of the node with :0/:1/:2
+
+    def quantized_input(owner, k, inp):
+        """Returns the node name whose :0/:1/:2 are the quantized inp."""
+        src = by_name.get(graph_util._base_name(inp))
+        if src is not None and _is_float_const(src) and ':' not in inp:
+            base = src['name']
+            if base not in const_done:
+                const_done.add(base)
+                out.extend(_quantized_const_nodes(base, _const_value(src)))
+            return ('const', base)
+        p = '%s/in%d/' % (owner, k)
+        dev = by_name[owner].get('device', '')
+        made = [
+            _make_const(p + 'reshape_dims', np.array([-1], np.int32), _I32),
+            _node(p + 'reshape', 'Reshape', [inp, p + 'reshape_dims'],
+                  {'T': ('type', _F32), 'Tshape': ('type', _I32)}, dev),
+            _make_const(p + 'reduction_dims', np.array([0], np.int32), _I32),
+            _node(p + 'min', 'Min', [p + 'reshape', p + 'reduction_dims'],
+                  {'T': ('type', _F32), 'Tidx': ('type', _I32),
+                   'keep_dims': ('b', False)}, dev),
+            _node(p + 'max', 'Max', [p + 'reshape', p + 'reduction_dims'],
+                  {'T': ('type', _F32), 'Tidx': ('type', _I32),
+                   'keep_dims': ('b', False)}, dev),
+            _node(p + 'quantize', 'QuantizeV2', [inp, p + 'min', p + 'max'],
+                  {'T': ('type', _U8), 'mode': ('s', b'MIN_COMBINED')}, dev),
+        ]
+        out.extend(made)
+        groups.append({'source': graph_util._base_name(inp),
+                       'names': {m['name'] for m in made},
+                       'out': p + 'quantize'})
+        return ('node', p + 'quantize')
+
+    def triple(ref):
+        kind, name = ref
+        if kind == 'const':
+            return [name + '/quint8_const', name + '/min', name + '/max']
+        return [name + ':0', name + ':1', name + ':2']
+
+    # ---- first pass ----
+    for n in nodes:
+        rw = _REWRITES.get(n['op'])
+        if rw is None or not _is_f32(n) or not rw[3](n) or \
+                any(i.startswith('^') for i in n['input']):
+            out.append(n)
+            continue
+        qop, q_inputs, is_i32, _, keep = rw
+        name, dev = n['name'], n.get('device', '')
+        refs = [quantized_input(name, k, n['input'][k]) for k in q_inputs]
+        ts = [triple(r) for r in refs]
+        # tensors first, then the other inputs, then the ranges in order
+        ins = [t[0] for t in ts] + n['input'][len(q_inputs):]
+        for t in ts:
+            ins += t[1:]
+        attr = {k: n['attr'][k] for k in keep if k in n['attr']}
+        if qop == 'QuantizedReshape':
+            attr['T'] = ('type', _U8)
+        last = name + '/eightbit'
+        out.append(_node(last, qop, ins, attr, dev))
+        if is_i32:
+            if fallback_min is None:
+                out.append(_node(name + '/requant_range',
+                                 'RequantizationRange',
+                                 [last + ':0', last + ':1', last + ':2'],
+                                 {'Tinput': ('type', _I32)}, dev))
+                rng = [name + '/requant_range:0', name + '/requant_range:1']
+            else:
+                out.append(_make_const(
+                    name + '/fallback_min',
+                    np.array(float(fallback_min), np.float32), _F32))
+                out.append(_make_const(
+                    name + '/fallback_max',
+                    np.array(float(fallback_max), np.float32), _F32))
+                rng = [name + '/fallback_min', name + '/fallback_max']
+            out.append(_node(name + '/requantize', 'Requantize',
+                             [last + ':0', last + ':1', last + ':2'] + rng,
+                             {'Tinput': ('type', _I32),
+                              'out_type': ('type', _U8)}, dev))
+            last = name + '/requantize'
+        out.append(_dequantize(name, last, dev))
+        dequantized[name] = last
+
+    # ---- second pass ----
+    group_of = {}
+    for g in groups:
+        for m in g['names']:
+            group_of[m] = g
+    users = {}  # node name -> set of consumer node names
+    for n in out:
+        for i in n['input']:
+            users.setdefault(graph_util._base_name(i), set()).add(n['name'])
+    drop = set()
+    rewire = {}  # group output node -> node with the uint8 triple
+    for name, last in dequantized.items():
+        if name in protected:
+            continue
+        consumers = users.get(name, set())
+        if not consumers or not all(
+                c in group_of and group_of[c]['source'] == name
+                for c in consumers):
+            continue
+        drop.add(name)
+        for g in groups:
+            if g['source'] == name:
+                drop |= g['names']
+                rewire[g['out']] = last
+
+    result = []
+    for n in out:
+        if n['name'] in drop:
+            continue
+        n = dict(n)
+        fixed = []
+        for i in n['input']:
+            base, _, port = i.partition(':')
+            if base in rewire:
+                i = '%s:%s' % (rewire[base], port or '0')
+            fixed.append(i)
+        n['input'] = fixed
+        result.append(n)
+    gd = graph_util._serialize(result)
+    # the float Consts whose consumers all went to 8 bit are dead now
+    return graph_util.extract_sub_graph(gd, list(outputs)) if outputs else gd

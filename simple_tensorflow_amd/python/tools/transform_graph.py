@@ -90,7 +90,28 @@ def sort_by_execution_order(gd, inputs, outputs, params):
     return graph_util._serialize(order)
 
 
+def _one(params, key, convert, default=None):
+    vals = params.get(key)
+    return convert(vals[-1]) if vals else default
+
+
+def quantize_weights(gd, inputs, outputs, params):
+    from simple_tensorflow_amd.python.tools import quantize_graph_lib
+    return quantize_graph_lib.quantize_weights(
+        gd, minimum_size=_one(params, 'minimum_size', int, 1024))
+
+
+def quantize_nodes(gd, inputs, outputs, params):
+    from simple_tensorflow_amd.python.tools import quantize_graph_lib
+    return quantize_graph_lib.quantize_nodes(
+        gd, inputs, outputs,
+        fallback_min=_one(params, 'fallback_min', float),
+        fallback_max=_one(params, 'fallback_max', float))
+
+
 TRANSFORMS = {
+    'quantize_weights': quantize_weights,
+    'quantize_nodes': quantize_nodes,
     'strip_unused_nodes': strip_unused_nodes,
     'remove_nodes': remove_nodes,
     'fold_batch_norms': fold_batch_norms,

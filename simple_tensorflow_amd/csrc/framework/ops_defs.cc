@@ -245,6 +245,9 @@ REGISTER_OP("RequantizationRange").Input("input: Tinput").Input("input_min: floa
 REGISTER_OP("Requantize").Input("input: Tinput").Input("input_min: float").Input("input_max: float").Input("requested_output_min: float").Input("requested_output_max: float").Output("output: out_type").Output("output_min: float").Output("output_max: float").Attr("Tinput: {int32} = int32").Attr("out_type: {uint8} = uint8");
 REGISTER_OP("QuantizedBiasAdd").Input("input: T1").Input("bias: T2").Input("min_input: float").Input("max_input: float").Input("min_bias: float").Input("max_bias: float").Output("output: out_type").Output("min_out: float").Output("max_out: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("out_type: {int32} = int32");
 REGISTER_OP("QuantizedMaxPool").Input("input: T").Input("min_input: float").Input("max_input: float").Output("output: T").Output("min_output: float").Output("max_output: float").Attr("T: {uint8} = uint8").Attr("ksize: list(int)").Attr("strides: list(int)").Attr("padding: string");
+REGISTER_OP("QuantizedAvgPool").Input("input: T").Input("min_input: float").Input("max_input: float").Output("output: T").Output("min_output: float").Output("max_output: float").Attr("T: {uint8} = uint8").Attr("ksize: list(int)").Attr("strides: list(int)").Attr("padding: string");
+REGISTER_OP("QuantizedRelu6").Input("features: T").Input("min_features: float").Input("max_features: float").Output("activations: T").Output("min_activations: float").Output("max_activations: float").Attr("T: {uint8} = uint8");
+REGISTER_OP("QuantizedConcat").Input("concat_dim: int32").Input("values: N * T").Input("input_mins: N * float").Input("input_maxes: N * float").Output("output: T").Output("output_min: float").Output("output_max: float").Attr("N: int >= 2").Attr("T: {uint8} = uint8");
 REGISTER_OP("QuantizedReshape").Input("tensor: T").Input("shape: int32").Input("input_min: float").Input("input_max: float").Output("output: T").Output("output_min: float").Output("output_max: float").Attr("T: {uint8, int32} = uint8");
 
 // --------------------------- linear algebra --------------------------------

@@ -350,63 +350,60 @@ class QuantizedBiasAddOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("QuantizedBiasAdd").Device(DEVICE_CPU),
                         QuantizedBiasAddOp);
 
-// NHWC max over the taps inside the image; geometry as GetPoolParams of
-// cpu_nn.cc. The mapping is monotone, so the ranges pass through.
-class QuantizedMaxPoolOp : public OpKernel {
+// Attributes, argument checks and geometry (GetPoolParams of cpu_nn.cc) of
+// the two NHWC quint8 pools. Both pass their ranges through.
+class QuantizedPoolOp : public OpKernel {
  public:
-  explicit QuantizedMaxPoolOp(OpKernelConstruction* c) : OpKernel(c) {
+  QuantizedPoolOp(OpKernelConstruction* c, const char* name)
+      : OpKernel(c), name_(name) {
     c->GetAttr("ksize", &ksize_);
     c->GetAttr("strides", &strides_);
     c->GetAttr("padding", &padding_);
   }
-  void Compute(OpKernelContext* ctx) override {
-    const Tensor& in = ctx->input(0);
-    OP_REQUIRES(ctx, in.dims() == 4,
-                errors::InvalidArgument("QuantizedMaxPool needs rank-4 "
-                                        "input"));
-    OP_REQUIRES(ctx, ksize_.size() == 4 && strides_.size() == 4 &&
-                         ksize_[1] >= 1 && ksize_[2] >= 1 &&
-                         strides_[1] >= 1 && strides_[2] >= 1,
-                errors::InvalidArgument("QuantizedMaxPool ksize and strides "
-                                        "must be [1, h, w, 1]"));
-    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
-                errors::InvalidArgument("QuantizedMaxPool padding must be "
-                                        "SAME or VALID"));
-    int64_t N = in.dim_size(0), H = in.dim_size(1), W = in.dim_size(2),
-            C = in.dim_size(3);
-    int64_t kh = ksize_[1], kw = ksize_[2], sh = strides_[1],
-            sw = strides_[2], P, Q, pad_h = 0, pad_w = 0;
-    if (padding_ == "SAME") {
-      P = (H + sh - 1) / sh;
-      Q = (W + sw - 1) / sw;
-      pad_h = std::max<int64_t>(0, (P - 1) * sh + kh - H) / 2;
-      pad_w = std::max<int64_t>(0, (Q - 1) * sw + kw - W) / 2;
-    } else {
-      P = (H - kh) / sh + 1;
-      Q = (W - kw) / sw + 1;
+
+ protected:
+  struct Geom {
+    int64_t N, H, W, C, kh, kw, sh, sw, P, Q, pad_h, pad_w;
+  };
+  // False, with the status set, when the arguments are invalid.
+  bool Geometry(OpKernelContext* ctx, const Tensor& in, Geom* g) const {
+    const char* what = nullptr;
+    if (in.dims() != 4) {
+      what = " needs rank-4 input";
+    } else if (!(ksize_.size() == 4 && strides_.size() == 4 &&
+                 ksize_[1] >= 1 && ksize_[2] >= 1 && strides_[1] >= 1 &&
+                 strides_[2] >= 1)) {
+      what = " ksize and strides must be [1, h, w, 1]";
+    } else if (padding_ != "SAME" && padding_ != "VALID") {
+      what = " padding must be SAME or VALID";
     }
-    OP_REQUIRES(ctx, P >= 0 && Q >= 0,
-                errors::InvalidArgument("QuantizedMaxPool window larger "
-                                        "than the VALID input"));
-    Tensor* out = ctx->allocate_output(0, TensorShape({N, P, Q, C}));
-    const uint8_t* x = in.flat<uint8_t>();
-    uint8_t* y = out->flat<uint8_t>();
-    for (int64_t n = 0; n < N; ++n)
-      for (int64_t p = 0; p < P; ++p)
-        for (int64_t q = 0; q < Q; ++q) {
-          uint8_t* o = y + ((n * P + p) * Q + q) * C;
-          std::fill(o, o + C, (uint8_t)0);
-          for (int64_t r = 0; r < kh; ++r) {
-            int64_t ih = p * sh - pad_h + r;
-            if (ih < 0 || ih >= H) continue;
-            for (int64_t s = 0; s < kw; ++s) {
-              int64_t iw = q * sw - pad_w + s;
-              if (iw < 0 || iw >= W) continue;
-              const uint8_t* xr = x + ((n * H + ih) * W + iw) * C;
-              for (int64_t c = 0; c < C; ++c) o[c] = std::max(o[c], xr[c]);
-            }
-          }
-        }
+    if (!what) {
+      g->N = in.dim_size(0);
+      g->H = in.dim_size(1);
+      g->W = in.dim_size(2);
+      g->C = in.dim_size(3);
+      g->kh = ksize_[1];
+      g->kw = ksize_[2];
+      g->sh = strides_[1];
+      g->sw = strides_[2];
+      g->pad_h = g->pad_w = 0;
+      if (padding_ == "SAME") {
+        g->P = (g->H + g->sh - 1) / g->sh;
+        g->Q = (g->W + g->sw - 1) / g->sw;
+        g->pad_h =
+            std::max<int64_t>(0, (g->P - 1) * g->sh + g->kh - g->H) / 2;
+        g->pad_w =
+            std::max<int64_t>(0, (g->Q - 1) * g->sw + g->kw - g->W) / 2;
+      } else {
+        g->P = (g->H - g->kh) / g->sh + 1;
+        g->Q = (g->W - g->kw) / g->sw + 1;
+      }
+      if (g->P < 0 || g->Q < 0) what = " window larger than the VALID input";
+    }
+    if (what) ctx->SetStatus(errors::InvalidArgument(name_, what));
+    return !what;
+  }
+  void ForwardRanges(OpKernelContext* ctx) const {
     ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
         ctx->input(1).flat<float>()[0];
     ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
@@ -414,11 +411,186 @@ class QuantizedMaxPoolOp : public OpKernel {
   }
 
  private:
+  const char* name_;
   std::vector<int64_t> ksize_, strides_;
   std::string padding_;
 };
+
+// NHWC max over the taps inside the image. The mapping is monotone, so the
+// ranges pass through.
+class QuantizedMaxPoolOp : public QuantizedPoolOp {
+ public:
+  explicit QuantizedMaxPoolOp(OpKernelConstruction* c)
+      : QuantizedPoolOp(c, "QuantizedMaxPool") {}
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Geom g;
+    if (!Geometry(ctx, in, &g)) return;
+    Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.C}));
+    const uint8_t* x = in.flat<uint8_t>();
+    uint8_t* y = out->flat<uint8_t>();
+    for (int64_t n = 0; n < g.N; ++n)
+      for (int64_t p = 0; p < g.P; ++p)
+        for (int64_t q = 0; q < g.Q; ++q) {
+          uint8_t* o = y + ((n * g.P + p) * g.Q + q) * g.C;
+          std::fill(o, o + g.C, (uint8_t)0);
+          for (int64_t r = 0; r < g.kh; ++r) {
+            int64_t ih = p * g.sh - g.pad_h + r;
+            if (ih < 0 || ih >= g.H) continue;
+            for (int64_t s = 0; s < g.kw; ++s) {
+              int64_t iw = q * g.sw - g.pad_w + s;
+              if (iw < 0 || iw >= g.W) continue;
+              const uint8_t* xr = x + ((n * g.H + ih) * g.W + iw) * g.C;
+              for (int64_t c = 0; c < g.C; ++c)
+                o[c] = std::max(o[c], xr[c]);
+            }
+          }
+        }
+    ForwardRanges(ctx);
+  }
+};
 REGISTER_KERNEL_BUILDER(Name("QuantizedMaxPool").Device(DEVICE_CPU),
                         QuantizedMaxPoolOp);
+
+// NHWC integer mean over the taps inside the image (the reference's
+// SpatialAvgPool<int32>): the divisor is the in-image tap count, not kh*kw,
+// and the division truncates. The mean of values in [mn, mx] lies in
+// [mn, mx], so the ranges pass through.
+class QuantizedAvgPoolOp : public QuantizedPoolOp {
+ public:
+  explicit QuantizedAvgPoolOp(OpKernelConstruction* c)
+      : QuantizedPoolOp(c, "QuantizedAvgPool") {}
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Geom g;
+    if (!Geometry(ctx, in, &g)) return;
+    Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.C}));
+    const uint8_t* x = in.flat<uint8_t>();
+    uint8_t* y = out->flat<uint8_t>();
+    std::vector<int32_t> acc(g.C);
+    for (int64_t n = 0; n < g.N; ++n)
+      for (int64_t p = 0; p < g.P; ++p)
+        for (int64_t q = 0; q < g.Q; ++q) {
+          std::fill(acc.begin(), acc.end(), 0);
+          int32_t taps = 0;
+          for (int64_t r = 0; r < g.kh; ++r) {
+            int64_t ih = p * g.sh - g.pad_h + r;
+            if (ih < 0 || ih >= g.H) continue;
+            for (int64_t s = 0; s < g.kw; ++s) {
+              int64_t iw = q * g.sw - g.pad_w + s;
+              if (iw < 0 || iw >= g.W) continue;
+              const uint8_t* xr = x + ((n * g.H + ih) * g.W + iw) * g.C;
+              for (int64_t c = 0; c < g.C; ++c) acc[c] += xr[c];
+              ++taps;
+            }
+          }
+          uint8_t* o = y + ((n * g.P + p) * g.Q + q) * g.C;
+          // a window always holds a tap inside the image; 0 guards the rest
+          for (int64_t c = 0; c < g.C; ++c)
+            o[c] = taps ? (uint8_t)(acc[c] / taps) : 0;
+        }
+    ForwardRanges(ctx);
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedAvgPool").Device(DEVICE_CPU),
+                        QuantizedAvgPoolOp);
+
+// out = min(max(x, lo), hi) with lo the clamped zero point and hi the quint8
+// of 6.0 (kernels/quantized_util.h). QuantizedRelu wraps a zero point above
+// 255 into the byte; Relu6 clamps it instead. The order is max, then min:
+// where hi < lo the result is hi.
+class QuantizedRelu6Op : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    float mn = ctx->input(1).flat<float>()[0];
+    float mx = ctx->input(2).flat<float>()[0];
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    int32_t lo = QuantRelu6Floor(mn, mx);
+    int32_t hi = QuantRelu6Ceil(mn, mx);
+    const uint8_t* p = in.flat<uint8_t>();
+    uint8_t* o = out->flat<uint8_t>();
+    for (int64_t i = 0; i < in.NumElements(); ++i)
+      o[i] = (uint8_t)std::min(std::max<int32_t>(p[i], lo), hi);
+    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = mn;
+    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = mx;
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedRelu6").Device(DEVICE_CPU),
+                        QuantizedRelu6Op);
+
+// Concatenation of N quint8 tensors that each carry a range of their own
+// (reference quantized_concat_op.cc analog). The output range is
+// [min(0, min_i mn_i), max_i mx_i]. An input whose range equals it, under
+// f32 == on both ends, is copied byte for byte; every other input goes
+// through RequantizeU8. The copy rule is part of the specification: for the
+// degenerate range (0, 0) requantizing maps every byte to 0.
+class QuantizedConcatOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    int n = (num_inputs() - 1) / 3;
+    const Tensor& first = ctx->input(1);
+    int rank = first.dims();
+    int64_t axis = IntVector(ctx->input(0))[0];
+    OP_REQUIRES(ctx, axis >= -rank && axis < rank,
+                errors::InvalidArgument("QuantizedConcat: concat_dim ", axis,
+                                        " out of range for rank ", rank));
+    if (axis < 0) axis += rank;
+    int64_t axis_total = 0;
+    for (int k = 0; k < n; ++k) {
+      const Tensor& t = ctx->input(1 + k);
+      OP_REQUIRES(ctx, t.dims() == rank,
+                  errors::InvalidArgument("QuantizedConcat: input ", k,
+                                          " has rank ", t.dims(),
+                                          ", input 0 has rank ", rank));
+      for (int d = 0; d < rank; ++d)
+        OP_REQUIRES(ctx, d == axis || t.dim_size(d) == first.dim_size(d),
+                    errors::InvalidArgument(
+                        "QuantizedConcat: input ", k, " has shape ",
+                        t.shape().DebugString(), ", input 0 has shape ",
+                        first.shape().DebugString(),
+                        "; they may differ on the concat axis only"));
+      axis_total += t.dim_size((int)axis);
+    }
+    TensorShape out_shape = first.shape();
+    out_shape.set_dim((int)axis, axis_total);
+    Tensor* out = ctx->allocate_output(0, out_shape);
+    int64_t outer = 1, inner = 1;
+    for (int i = 0; i < axis; ++i) outer *= first.dim_size(i);
+    for (int i = (int)axis + 1; i < rank; ++i) inner *= first.dim_size(i);
+    float lo = 0, hi = 0;
+    for (int k = 0; k < n; ++k)
+      QuantConcatRangeFold(ctx->input(1 + n + k).flat<float>()[0],
+                           ctx->input(1 + 2 * n + k).flat<float>()[0],
+                           k == 0, &lo, &hi);
+    uint8_t* dst = out->flat<uint8_t>();
+    int64_t out_row = axis_total * inner;
+    int64_t off = 0;
+    for (int k = 0; k < n; ++k) {
+      const Tensor& t = ctx->input(1 + k);
+      float mn = ctx->input(1 + n + k).flat<float>()[0];
+      float mx = ctx->input(1 + 2 * n + k).flat<float>()[0];
+      int64_t row = t.dim_size((int)axis) * inner;
+      const uint8_t* src = t.flat<uint8_t>();
+      uint8_t lut[256];
+      bool copy = mn == lo && mx == hi;
+      for (int v = 0; v < 256; ++v)
+        lut[v] = copy ? (uint8_t)v : RequantizeU8(v, mn, mx, lo, hi);
+      for (int64_t o = 0; o < outer; ++o) {
+        const uint8_t* s = src + o * row;
+        uint8_t* d = dst + o * out_row + off;
+        for (int64_t j = 0; j < row; ++j) d[j] = lut[s[j]];
+      }
+      off += row;
+    }
+    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = lo;
+    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = hi;
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedConcat").Device(DEVICE_CPU),
+                        QuantizedConcatOp);
 
 // Reshape with the two range scalars forwarded. Like ReshapeOp it shares
 // the buffers and touches no tensor data, so one class serves both devices.

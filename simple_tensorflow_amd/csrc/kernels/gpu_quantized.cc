@@ -1,11 +1,12 @@
 // GPU OpKernels: the quantized family (QuantizeV2, Dequantize,
 // QuantizedMatMul, QuantizedConv2D, QuantizedRelu, RequantizationRange,
 // QuantizeDownAndShrinkRange, Requantize, QuantizedBiasAdd,
-// QuantizedMaxPool) on kernels/hip/gemm_i8.hip and
-// kernels/hip/quantized.hip.
+// QuantizedMaxPool, QuantizedAvgPool, QuantizedRelu6, QuantizedConcat) on
+// kernels/hip/gemm_i8.hip and kernels/hip/quantized.hip.
 //
-// The min/max ranges live in device memory on both sides of every op: no
-// argument is in host memory and nothing here reads a range value. The
+// The min/max ranges live in device memory on both sides of every op: only
+// QuantizedConcat's axis is in host memory and nothing here reads a range
+// value. The
 // kernels derive zero points and steps from the device scalars and write
 // the output ranges themselves, so a chain of quantized layers has no
 // device-to-host sync and replays inside a captured step.
@@ -295,9 +296,18 @@ class GpuQuantizedBiasAddOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("QuantizedBiasAdd").Device(DEVICE_GPU),
                         GpuQuantizedBiasAddOp);
 
-class GpuQuantizedMaxPoolOp : public OpKernel {
+// QuantizedMaxPool and QuantizedAvgPool: the same attributes, checks and
+// geometry in front of two entry points of one signature.
+using QuantizedPoolFn = hipError_t (*)(const uint8_t*, const float*,
+                                       const float*, uint8_t*, float*,
+                                       float*, const StfPoolGeom*,
+                                       hipStream_t);
+
+class GpuQuantizedPoolOp : public OpKernel {
  public:
-  explicit GpuQuantizedMaxPoolOp(OpKernelConstruction* c) : OpKernel(c) {
+  GpuQuantizedPoolOp(OpKernelConstruction* c, const char* name,
+                     QuantizedPoolFn fn)
+      : OpKernel(c), name_(name), fn_(fn) {
     c->GetAttr("ksize", &ksize_);
     c->GetAttr("strides", &strides_);
     c->GetAttr("padding", &padding_);
@@ -305,16 +315,15 @@ class GpuQuantizedMaxPoolOp : public OpKernel {
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     OP_REQUIRES(ctx, x.dims() == 4,
-                errors::InvalidArgument("QuantizedMaxPool needs rank-4 "
-                                        "input"));
+                errors::InvalidArgument(name_, " needs rank-4 input"));
     OP_REQUIRES(ctx, ksize_.size() == 4 && strides_.size() == 4 &&
                          ksize_[1] >= 1 && ksize_[2] >= 1 &&
                          strides_[1] >= 1 && strides_[2] >= 1,
-                errors::InvalidArgument("QuantizedMaxPool ksize and strides "
-                                        "must be [1, h, w, 1]"));
+                errors::InvalidArgument(name_, " ksize and strides must be "
+                                               "[1, h, w, 1]"));
     OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
-                errors::InvalidArgument("QuantizedMaxPool padding must be "
-                                        "SAME or VALID"));
+                errors::InvalidArgument(name_, " padding must be SAME or "
+                                               "VALID"));
     StfPoolGeom g;
     g.N = (int)x.dim_size(0);
     g.H = (int)x.dim_size(1);
@@ -335,25 +344,126 @@ class GpuQuantizedMaxPoolOp : public OpKernel {
       g.ph = g.pw = 0;
     }
     OP_REQUIRES(ctx, g.P >= 0 && g.Q >= 0,
-                errors::InvalidArgument("QuantizedMaxPool window larger "
-                                        "than the VALID input"));
+                errors::InvalidArgument(name_, " window larger than the "
+                                               "VALID input"));
     Tensor* y = ctx->allocate_output(
         0, TensorShape({(int64_t)g.N, (int64_t)g.P, (int64_t)g.Q,
                         (int64_t)g.C}));
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
-    OP_HIP_OK(ctx, stf_quantized_max_pool(
-                       (const uint8_t*)x.raw_data(), F32(ctx->input(1)),
+    OP_HIP_OK(ctx, fn_((const uint8_t*)x.raw_data(), F32(ctx->input(1)),
                        F32(ctx->input(2)), (uint8_t*)y->raw_data(), omn, omx,
                        &g, GPU_STREAM(ctx)));
   }
 
  private:
+  const char* name_;
+  QuantizedPoolFn fn_;
   std::vector<int64_t> ksize_, strides_;
   std::string padding_;
 };
+class GpuQuantizedMaxPoolOp : public GpuQuantizedPoolOp {
+ public:
+  explicit GpuQuantizedMaxPoolOp(OpKernelConstruction* c)
+      : GpuQuantizedPoolOp(c, "QuantizedMaxPool", stf_quantized_max_pool) {}
+};
+class GpuQuantizedAvgPoolOp : public GpuQuantizedPoolOp {
+ public:
+  explicit GpuQuantizedAvgPoolOp(OpKernelConstruction* c)
+      : GpuQuantizedPoolOp(c, "QuantizedAvgPool", stf_quantized_avg_pool) {}
+};
 REGISTER_KERNEL_BUILDER(Name("QuantizedMaxPool").Device(DEVICE_GPU),
                         GpuQuantizedMaxPoolOp);
+REGISTER_KERNEL_BUILDER(Name("QuantizedAvgPool").Device(DEVICE_GPU),
+                        GpuQuantizedAvgPoolOp);
+
+class GpuQuantizedRelu6Op : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& in = ctx->input(0);
+    Tensor* out = ctx->allocate_output(0, in.shape());
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    OP_HIP_OK(ctx, stf_quantized_relu6((const uint8_t*)in.raw_data(),
+                                       F32(ctx->input(1)), F32(ctx->input(2)),
+                                       (uint8_t*)out->raw_data(), omn, omx,
+                                       in.NumElements(), GPU_STREAM(ctx)));
+  }
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedRelu6").Device(DEVICE_GPU),
+                        GpuQuantizedRelu6Op);
+
+// Only concat_dim is in host memory. The N range pairs stay on the device:
+// a range pass over all chunks of kStfQuantConcatMax inputs leaves the
+// output range in the two output scalars, then one copy launch per chunk
+// reads it from there.
+class GpuQuantizedConcatOp : public OpKernel {
+ public:
+  using OpKernel::OpKernel;
+  void Compute(OpKernelContext* ctx) override {
+    int n = (num_inputs() - 1) / 3;
+    const Tensor& first = ctx->input(1);
+    int rank = first.dims();
+    int64_t axis = IntVector(ctx->input(0))[0];
+    OP_REQUIRES(ctx, axis >= -rank && axis < rank,
+                errors::InvalidArgument("QuantizedConcat: concat_dim ", axis,
+                                        " out of range for rank ", rank));
+    if (axis < 0) axis += rank;
+    int64_t axis_total = 0;
+    for (int k = 0; k < n; ++k) {
+      const Tensor& t = ctx->input(1 + k);
+      OP_REQUIRES(ctx, t.dims() == rank,
+                  errors::InvalidArgument("QuantizedConcat: input ", k,
+                                          " has rank ", t.dims(),
+                                          ", input 0 has rank ", rank));
+      for (int d = 0; d < rank; ++d)
+        OP_REQUIRES(ctx, d == axis || t.dim_size(d) == first.dim_size(d),
+                    errors::InvalidArgument(
+                        "QuantizedConcat: input ", k, " has shape ",
+                        t.shape().DebugString(), ", input 0 has shape ",
+                        first.shape().DebugString(),
+                        "; they may differ on the concat axis only"));
+      axis_total += t.dim_size((int)axis);
+    }
+    TensorShape out_shape = first.shape();
+    out_shape.set_dim((int)axis, axis_total);
+    Tensor* y = ctx->allocate_output(0, out_shape);
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    int64_t outer = 1, inner = 1;
+    for (int i = 0; i < axis; ++i) outer *= first.dim_size(i);
+    for (int i = (int)axis + 1; i < rank; ++i) inner *= first.dim_size(i);
+    hipStream_t s = GPU_STREAM(ctx);
+    std::vector<StfQuantConcatArgs> chunks;
+    int64_t off = 0;
+    for (int k = 0; k < n; ++k) {
+      if (k % kStfQuantConcatMax == 0) {
+        chunks.emplace_back();
+        chunks.back().n = 0;
+      }
+      StfQuantConcatArgs& a = chunks.back();
+      const Tensor& t = ctx->input(1 + k);
+      int j = a.n++;
+      a.src[j] = (const uint8_t*)t.raw_data();
+      a.mn[j] = F32(ctx->input(1 + n + k));
+      a.mx[j] = F32(ctx->input(1 + 2 * n + k));
+      a.inner[j] = t.dim_size((int)axis) * inner;
+      a.off[j] = off;
+      off += a.inner[j];
+    }
+    for (size_t c = 0; c < chunks.size(); ++c)
+      OP_HIP_OK(ctx, stf_quantized_concat_range(&chunks[c], c == 0, omn, omx,
+                                                s));
+    for (size_t c = 0; c < chunks.size(); ++c)
+      OP_HIP_OK(ctx, stf_quantized_concat_copy(&chunks[c], omn, omx,
+                                               (uint8_t*)y->raw_data(), outer,
+                                               off, s));
+  }
+};
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedConcat").Device(DEVICE_GPU).HostMemory("concat_dim"),
+    GpuQuantizedConcatOp);
 
 // QuantizedReshape moves no data: its one kernel class is registered for
 // both devices in kernels/cpu_quantized.cc, as Reshape's is in cpu_basic.cc.

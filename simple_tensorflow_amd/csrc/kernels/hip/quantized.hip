@@ -1,6 +1,7 @@
 // Elementwise and range kernels of the quantized ops: QuantizeV2,
 // Dequantize, QuantizedRelu, RequantizationRange, QuantizeDownAndShrinkRange,
-// Requantize, QuantizedBiasAdd, QuantizedMaxPool.
+// Requantize, QuantizedBiasAdd, QuantizedMaxPool, QuantizedAvgPool,
+// QuantizedRelu6, QuantizedConcat.
 //
 // Every output is bit-equal to kernels/cpu_quantized.cc: the same IEEE
 // operations in the same order and precision (f32 for the quint8 paths, f64
@@ -463,6 +464,252 @@ __global__ void QuantizedMaxPoolKernel(const uint8_t* __restrict__ x,
   }
 }
 
+// Sums of the four u8 lanes of a word, in 32 bits: 255 * taps overflows 16
+// bits once a window has more than 257 taps, and 32 bits hold any window.
+__device__ __forceinline__ void AddU8x4(uint32_t w, uint32_t* acc) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b) acc[b] += (w >> (8 * b)) & 0xff;
+}
+
+__device__ __forceinline__ void AddU8x16(uint4 v, uint32_t* acc) {
+  AddU8x4(v.x, acc);
+  AddU8x4(v.y, acc + 4);
+  AddU8x4(v.z, acc + 8);
+  AddU8x4(v.w, acc + 12);
+}
+
+// The integer division is the CPU kernel's: a float reciprocal turns
+// 255 * cnt / cnt into 254 for some counts.
+__device__ __forceinline__ uint32_t DivU8x4(const uint32_t* acc,
+                                            uint32_t cnt) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) o |= (acc[b] / cnt) << (8 * b);
+  return o;
+}
+
+// Taps of the clipped window; never 0 for a valid geometry, and 1 keeps the
+// division defined where it would be.
+__device__ __forceinline__ uint32_t PoolTaps(int h0, int h1, int w0, int w1) {
+  int cnt = max(h1 - h0, 0) * max(w1 - w0, 0);
+  return cnt > 0 ? (uint32_t)cnt : 1u;
+}
+
+// QuantizedMaxPoolV16Kernel's scheme with sixteen u32 sums per thread.
+__global__ void QuantizedAvgPoolV16Kernel(const uint8_t* __restrict__ x,
+                                          const float* __restrict__ mnp,
+                                          const float* __restrict__ mxp,
+                                          uint8_t* __restrict__ y,
+                                          float* __restrict__ out_mn,
+                                          float* __restrict__ out_mx,
+                                          StfPoolGeom g, int64_t total16) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = mnp[0];
+    out_mx[0] = mxp[0];
+  }
+  int64_t c16 = g.C / 16;
+  for (int64_t i = tid; i < total16; i += stride) {
+    int64_t rem = i;
+    int64_t cw = rem % c16; rem /= c16;
+    int q = (int)(rem % g.Q); rem /= g.Q;
+    int p = (int)(rem % g.P); rem /= g.P;
+    int64_t n = rem;
+    int h0, h1, w0, w1;
+    PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
+    uint32_t acc[16];
+#pragma unroll
+    for (int b = 0; b < 16; ++b) acc[b] = 0;
+    // Four taps of a row at a time, their loads issued before the first sum
+    // so that they are in flight together: a global-pool head (8x8 on 2048
+    // channels) has few threads with 64 taps each and is bound by the
+    // latency of a tap's load.
+    for (int ih = h0; ih < h1; ++ih) {
+      const uint8_t* row = x + ((n * g.H + ih) * g.W) * g.C + cw * 16;
+      int iw = w0;
+      for (; iw + 4 <= w1; iw += 4) {
+        const uint8_t* t = row + (int64_t)iw * g.C;
+        uint4 v0 = *(const uint4*)t;
+        uint4 v1 = *(const uint4*)(t + g.C);
+        uint4 v2 = *(const uint4*)(t + 2 * (int64_t)g.C);
+        uint4 v3 = *(const uint4*)(t + 3 * (int64_t)g.C);
+        AddU8x16(v0, acc);
+        AddU8x16(v1, acc);
+        AddU8x16(v2, acc);
+        AddU8x16(v3, acc);
+      }
+      for (; iw < w1; ++iw)
+        AddU8x16(*(const uint4*)(row + (int64_t)iw * g.C), acc);
+    }
+    uint32_t cnt = PoolTaps(h0, h1, w0, w1);
+    uint4 o;
+    o.x = DivU8x4(acc, cnt);
+    o.y = DivU8x4(acc + 4, cnt);
+    o.z = DivU8x4(acc + 8, cnt);
+    o.w = DivU8x4(acc + 12, cnt);
+    // ((n * P + p) * Q + q) * C + cw * 16 == i * 16
+    ((uint4*)y)[i] = o;
+  }
+}
+
+__global__ void QuantizedAvgPoolKernel(const uint8_t* __restrict__ x,
+                                       const float* __restrict__ mnp,
+                                       const float* __restrict__ mxp,
+                                       uint8_t* __restrict__ y,
+                                       float* __restrict__ out_mn,
+                                       float* __restrict__ out_mx,
+                                       StfPoolGeom g, int64_t total) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = mnp[0];
+    out_mx[0] = mxp[0];
+  }
+  for (int64_t i = tid; i < total; i += stride) {
+    int64_t rem = i;
+    int64_t c = rem % g.C; rem /= g.C;
+    int q = (int)(rem % g.Q); rem /= g.Q;
+    int p = (int)(rem % g.P); rem /= g.P;
+    int64_t n = rem;
+    int h0, h1, w0, w1;
+    PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
+    uint32_t sum = 0;
+    for (int ih = h0; ih < h1; ++ih)
+      for (int iw = w0; iw < w1; ++iw)
+        sum += x[((n * g.H + ih) * g.W + iw) * g.C + c];
+    y[i] = (uint8_t)(sum / PoolTaps(h0, h1, w0, w1));
+  }
+}
+
+__device__ __forceinline__ uint32_t PkMinU16(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(
+      uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a),
+                                          __builtin_bit_cast(u16x2, b)));
+}
+
+// min(max(., lo), hi) per byte of a word; lo2 and hi2 hold the clamp value
+// in both u16 halves, and the even and the odd bytes go through as u16
+// pairs (MaxU8x4Acc's scheme).
+__device__ __forceinline__ uint32_t ClampU8x4(uint32_t w, uint32_t lo2,
+                                              uint32_t hi2) {
+  uint32_t even = PkMinU16(PkMaxU16(w & 0x00ff00ffu, lo2), hi2);
+  uint32_t odd = PkMinU16(PkMaxU16((w >> 8) & 0x00ff00ffu, lo2), hi2);
+  return even | odd << 8;
+}
+
+// QuantizedReluKernel's scheme with a ceiling as well as a floor. Both clamp
+// values lie in 0..255 (kernels/quantized_util.h): QuantizedRelu wraps a
+// zero point above 255 into the byte, Relu6 clamps it.
+__global__ void QuantizedRelu6Kernel(const uint8_t* __restrict__ x,
+                                     const float* __restrict__ mnp,
+                                     const float* __restrict__ mxp,
+                                     uint8_t* __restrict__ y,
+                                     float* __restrict__ out_mn,
+                                     float* __restrict__ out_mx, int64_t n) {
+  float mn = mnp[0], mx = mxp[0];
+  int32_t lo = stf::QuantRelu6Floor(mn, mx);
+  int32_t hi = stf::QuantRelu6Ceil(mn, mx);
+  uint32_t lo2 = (uint32_t)lo | (uint32_t)lo << 16;
+  uint32_t hi2 = (uint32_t)hi | (uint32_t)hi << 16;
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (tid == 0) {
+    out_mn[0] = mn;
+    out_mx[0] = mx;
+  }
+  int64_t n16 = n / 16;
+  for (int64_t i = tid; i < n16; i += stride) {
+    uint4 v = ((const uint4*)x)[i];
+    v.x = ClampU8x4(v.x, lo2, hi2);
+    v.y = ClampU8x4(v.y, lo2, hi2);
+    v.z = ClampU8x4(v.z, lo2, hi2);
+    v.w = ClampU8x4(v.w, lo2, hi2);
+    ((uint4*)y)[i] = v;
+  }
+  for (int64_t i = n16 * 16 + tid; i < n; i += stride) {
+    int32_t p = x[i];
+    p = p > lo ? p : lo;
+    y[i] = (uint8_t)(p < hi ? p : hi);
+  }
+}
+
+// One thread folds a chunk's ranges into the two output scalars, in input
+// order, as the CPU kernel does.
+__global__ void QuantizedConcatRangeKernel(StfQuantConcatArgs a, int first,
+                                           float* __restrict__ out_mn,
+                                           float* __restrict__ out_mx) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  float lo = 0.f, hi = 0.f;
+  if (!first) {
+    lo = out_mn[0];
+    hi = out_mx[0];
+  }
+  for (int k = 0; k < a.n; ++k)
+    stf::QuantConcatRangeFold(a.mn[k][0], a.mx[k][0], first && k == 0, &lo,
+                              &hi);
+  out_mn[0] = lo;
+  out_mx[0] = hi;
+}
+
+__device__ __forceinline__ uint32_t LutU8x4(const uint8_t* lut, uint32_t w) {
+  return (uint32_t)lut[w & 0xff] | (uint32_t)lut[(w >> 8) & 0xff] << 8 |
+         (uint32_t)lut[(w >> 16) & 0xff] << 16 |
+         (uint32_t)lut[w >> 24] << 24;
+}
+
+// blockIdx.y picks the input of the chunk, blockIdx.x strides over its
+// [outer, inner] bytes; the block must have 256 threads. Each block first
+// builds its input's 256-entry table in LDS with the helper the CPU kernel
+// uses (RequantizeU8), one entry per thread, so the f32 work is done 256
+// times per block instead of once per byte and bit-equality with the CPU
+// needs no care in the copy loop. The table is one 256-byte LDS bank row: two
+// lookups conflict only on the same dword, which broadcasts. An input whose
+// range equals the output range (f32 == on both ends) is copied as it is,
+// which is the specified result and not the table's: requantizing under the
+// degenerate range (0, 0) would map every byte to 0.
+// VEC: every inner, column offset and pointer is a multiple of 16, and a
+// thread moves 16 bytes; otherwise one byte.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+QuantizedConcatCopyKernel(StfQuantConcatArgs a,
+                          const float* __restrict__ out_mn,
+                          const float* __restrict__ out_mx,
+                          uint8_t* __restrict__ y, int64_t outer,
+                          int64_t out_row) {
+  __shared__ __attribute__((aligned(256))) uint8_t lut[256];
+  int k = blockIdx.y;
+  int64_t width = VEC ? a.inner[k] / 16 : a.inner[k];
+  int64_t units = outer * width;
+  // uniform over the block: no thread of it has work
+  if ((int64_t)blockIdx.x * blockDim.x >= units) return;
+  float mn = a.mn[k][0], mx = a.mx[k][0];
+  float lo = out_mn[0], hi = out_mx[0];
+  bool copy = mn == lo && mx == hi;
+  lut[threadIdx.x] = stf::RequantizeU8(threadIdx.x, mn, mx, lo, hi);
+  __syncthreads();
+  const uint8_t* __restrict__ src = a.src[k];
+  uint8_t* __restrict__ dst = y + a.off[k];
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = tid; i < units; i += stride) {
+    int64_t row = i / width, col = i - row * width;
+    if (VEC) {
+      uint4 v = ((const uint4*)src)[i];
+      if (!copy) {
+        v.x = LutU8x4(lut, v.x);
+        v.y = LutU8x4(lut, v.y);
+        v.z = LutU8x4(lut, v.z);
+        v.w = LutU8x4(lut, v.w);
+      }
+      *(uint4*)(dst + row * out_row + col * 16) = v;
+    } else {
+      uint8_t v = src[i];
+      dst[row * out_row + col] = copy ? v : lut[v];
+    }
+  }
+}
+
 hipError_t MinMaxI32(const int32_t* x, int32_t* lohi, int64_t n,
                      hipStream_t stream) {
   hipError_t e = hipMemsetAsync(lohi, 0, 2 * sizeof(int32_t), stream);
@@ -575,5 +822,71 @@ extern "C" hipError_t stf_quantized_max_pool(const uint8_t* x,
     hipLaunchKernelGGL(QuantizedMaxPoolKernel, ElemwiseGrid(total, 256, 1),
                        dim3(256), 0, stream, x, mn, mx, y, out_mn, out_mx, g,
                        total);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantized_avg_pool(const uint8_t* x,
+                                             const float* mn, const float* mx,
+                                             uint8_t* y, float* out_mn,
+                                             float* out_mx,
+                                             const StfPoolGeom* gp,
+                                             hipStream_t stream) {
+  const StfPoolGeom g = *gp;
+  int64_t total = (int64_t)g.N * g.P * g.Q * g.C;
+  if (g.C > 0 && g.C % 16 == 0)
+    hipLaunchKernelGGL(QuantizedAvgPoolV16Kernel,
+                       ElemwiseGrid(total / 16, 256, 1), dim3(256), 0,
+                       stream, x, mn, mx, y, out_mn, out_mx, g, total / 16);
+  else
+    hipLaunchKernelGGL(QuantizedAvgPoolKernel, ElemwiseGrid(total, 256, 1),
+                       dim3(256), 0, stream, x, mn, mx, y, out_mn, out_mx, g,
+                       total);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantized_relu6(const uint8_t* x, const float* mn,
+                                          const float* mx, uint8_t* y,
+                                          float* out_mn, float* out_mx,
+                                          int64_t n, hipStream_t stream) {
+  // Two 16-byte groups per thread: a thread's prologue has one f32 divide
+  // more than QuantizedRelu's (profiles/quantized_inception.md).
+  hipLaunchKernelGGL(QuantizedRelu6Kernel, ElemwiseGrid(n, 256, 32),
+                     dim3(256), 0, stream, x, mn, mx, y, out_mn, out_mx, n);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantized_concat_range(const StfQuantConcatArgs* a,
+                                                 int first, float* out_mn,
+                                                 float* out_mx,
+                                                 hipStream_t stream) {
+  if (a->n < 1 || a->n > kStfQuantConcatMax) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(QuantizedConcatRangeKernel, dim3(1), dim3(64), 0, stream,
+                     *a, first, out_mn, out_mx);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t stf_quantized_concat_copy(const StfQuantConcatArgs* a,
+                                                const float* out_mn,
+                                                const float* out_mx,
+                                                uint8_t* y, int64_t outer,
+                                                int64_t out_row,
+                                                hipStream_t stream) {
+  if (a->n < 1 || a->n > kStfQuantConcatMax) return hipErrorInvalidValue;
+  bool vec = ((uintptr_t)y & 15) == 0 && out_row % 16 == 0;
+  int64_t widest = 0;
+  for (int k = 0; k < a->n; ++k) {
+    vec = vec && a->inner[k] % 16 == 0 && a->off[k] % 16 == 0 &&
+          ((uintptr_t)a->src[k] & 15) == 0;
+    widest = a->inner[k] > widest ? a->inner[k] : widest;
+  }
+  int64_t units = outer * (vec ? widest / 16 : widest);
+  if (units <= 0) return hipSuccess;
+  dim3 grid(ElemwiseGrid(units, 256, 4).x, (uint32_t)a->n);
+  if (vec)
+    hipLaunchKernelGGL(QuantizedConcatCopyKernel<true>, grid, dim3(256), 0,
+                       stream, *a, out_mn, out_mx, y, outer, out_row);
+  else
+    hipLaunchKernelGGL(QuantizedConcatCopyKernel<false>, grid, dim3(256), 0,
+                       stream, *a, out_mn, out_mx, y, outer, out_row);
   return hipGetLastError();
 }

@@ -189,6 +189,39 @@ hipError_t stf_quantized_max_pool(const uint8_t* x, const float* mn,
                                   const float* mx, uint8_t* y, float* out_mn,
                                   float* out_mx, const StfPoolGeom* g,
                                   hipStream_t stream);
+// NHWC quint8 integer mean over the in-image taps (sum / tap count,
+// truncating); the range is copied through.
+hipError_t stf_quantized_avg_pool(const uint8_t* x, const float* mn,
+                                  const float* mx, uint8_t* y, float* out_mn,
+                                  float* out_mx, const StfPoolGeom* g,
+                                  hipStream_t stream);
+hipError_t stf_quantized_relu6(const uint8_t* x, const float* mn,
+                               const float* mx, uint8_t* y, float* out_mn,
+                               float* out_mx, int64_t n, hipStream_t stream);
+// QuantizedConcat takes its inputs in chunks of at most kStfQuantConcatMax,
+// one table per chunk, passed by value to the kernels. Input k is viewed as
+// [outer, inner[k]] and lands at column off[k] of the [outer, out_row]
+// output; mn[k] / mx[k] are its device range scalars.
+constexpr int kStfQuantConcatMax = 16;
+struct StfQuantConcatArgs {
+  const uint8_t* src[kStfQuantConcatMax];
+  const float* mn[kStfQuantConcatMax];
+  const float* mx[kStfQuantConcatMax];
+  int64_t inner[kStfQuantConcatMax];
+  int64_t off[kStfQuantConcatMax];
+  int n;
+};
+// Folds the chunk's ranges into out_mn / out_mx: first starts the fold at
+// [min(0, mn[0]), mx[0]], later chunks continue from the stored values. Call
+// it for every chunk, in order, before the first stf_quantized_concat_copy.
+hipError_t stf_quantized_concat_range(const StfQuantConcatArgs* a, int first,
+                                      float* out_mn, float* out_mx,
+                                      hipStream_t stream);
+// Writes the chunk's columns of y. out_mn / out_mx hold the final range.
+hipError_t stf_quantized_concat_copy(const StfQuantConcatArgs* a,
+                                     const float* out_mn, const float* out_mx,
+                                     uint8_t* y, int64_t outer,
+                                     int64_t out_row, hipStream_t stream);
 
 // ---- depthwise.hip ----
 // Filter is [r, s, c, mult]; g->cout is unused.

@@ -801,11 +801,32 @@ def _quantized_matmul_shape(op):
 
 @RegisterShape('Requantize')
 @RegisterShape('QuantizedBiasAdd')
+@RegisterShape('QuantizedRelu6')
 def _quantized_same_shape(op):
     return [op.inputs[0]._shape, (), ()]
 
 
+@RegisterShape('QuantizedConcat')
+def _quantized_concat_shape(op):
+    n = op.get_attr('N')
+    shapes = [t._shape for t in op.inputs[1:1 + n]]
+    axis = getattr(op.inputs[0], '_const_value', None)
+    if axis is None or any(s is None for s in shapes) or \
+            any(len(s) != len(shapes[0]) for s in shapes):
+        return [None, (), ()]
+    rank = len(shapes[0])
+    axis = int(np.asarray(axis).reshape(-1)[0])
+    if not -rank <= axis < rank:
+        return [None, (), ()]
+    axis %= rank
+    dims = list(shapes[0])
+    sizes = [s[axis] for s in shapes]
+    dims[axis] = None if any(d is None for d in sizes) else sum(sizes)
+    return [tuple(dims), (), ()]
+
+
 @RegisterShape('QuantizedMaxPool')
+@RegisterShape('QuantizedAvgPool')
 def _quantized_max_pool_shape(op):
     x = op.inputs[0]._shape
     if x is None:

@@ -89,6 +89,31 @@ def quantized_max_pool(input, min_input, max_input, ksize,  # noqa: A002
                     strides=list(strides), padding=padding, name=name)
 
 
+def quantized_avg_pool(input, min_input, max_input, ksize,  # noqa: A002
+                       strides, padding, name=None):
+    """NHWC quint8 -> (quint8 output, min_output, max_output): the sum of
+    the taps inside the image over their number, in integer division."""
+    return apply_op('QuantizedAvgPool', input, convert_to_tensor(min_input),
+                    convert_to_tensor(max_input), ksize=list(ksize),
+                    strides=list(strides), padding=padding, name=name)
+
+
+def quantized_relu6(features, min_features, max_features, name=None):
+    return apply_op('QuantizedRelu6', features,
+                    convert_to_tensor(min_features),
+                    convert_to_tensor(max_features), name=name)
+
+
+def quantized_concat(concat_dim, values, input_mins, input_maxes, name=None):
+    """N quint8 tensors with a range each -> (quint8 output, output_min,
+    output_max) over [min(0, min of the mins), max of the maxes]."""
+    return apply_op('QuantizedConcat',
+                    convert_to_tensor(concat_dim, dtype=dtypes.int32),
+                    list(values),
+                    [convert_to_tensor(m) for m in input_mins],
+                    [convert_to_tensor(m) for m in input_maxes], name=name)
+
+
 def quantized_reshape(tensor, shape, input_min, input_max, name=None):
     return apply_op('QuantizedReshape', tensor,
                     convert_to_tensor(shape, dtype=dtypes.int32),
@@ -100,5 +125,6 @@ for _op in ('QuantizeV2', 'Dequantize', 'QuantizedMatMul', 'QuantizedRelu',
             'QuantizedConv2D',
             'QuantizeDownAndShrinkRange', 'RequantizationRange',
             'Requantize', 'QuantizedBiasAdd', 'QuantizedMaxPool',
+            'QuantizedAvgPool', 'QuantizedRelu6', 'QuantizedConcat',
             'QuantizedReshape'):
     NoGradient(_op)

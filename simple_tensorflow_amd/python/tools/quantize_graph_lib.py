@@ -141,26 +141,56 @@ def _nhwc(n):
     return _str_attr(n, 'data_format', 'NHWC') == 'NHWC'
 
 
-# op -> (quantized op, indices of the inputs to quantize, int32 result,
-#        can the quantized op express this node?, attributes carried over)
+def _concat_ok(n):
+    # QuantizedConcat takes an int32 axis; Concat has no Tidx
+    return _attr(n, 'N', 0) >= 2 and _attr(n, 'Tidx', _I32) == _I32
+
+
+def _first(count):
+    return lambda n: tuple(range(count))
+
+
+# The N values of a concat: behind the axis in Concat, before it in ConcatV2.
+def _concat_values(n):
+    return tuple(range(1, _attr(n, 'N') + 1))
+
+
+def _concat_v2_values(n):
+    return tuple(range(_attr(n, 'N')))
+
+
+# op -> (quantized op, node -> indices of the inputs to quantize, int32
+#        result, can the quantized op express this node?, attributes carried
+#        over)
 _REWRITES = {
-    'Conv2D': ('QuantizedConv2D', (0, 1), True, _conv_ok,
+    'Conv2D': ('QuantizedConv2D', _first(2), True, _conv_ok,
                ('strides', 'padding')),
-    'MatMul': ('QuantizedMatMul', (0, 1), True, lambda n: True,
+    'MatMul': ('QuantizedMatMul', _first(2), True, lambda n: True,
                ('transpose_a', 'transpose_b')),
-    'BiasAdd': ('QuantizedBiasAdd', (0, 1), True, _nhwc, ()),
-    'Relu': ('QuantizedRelu', (0,), False, lambda n: True, ()),
-    'MaxPool': ('QuantizedMaxPool', (0,), False, _pool_ok,
+    'BiasAdd': ('QuantizedBiasAdd', _first(2), True, _nhwc, ()),
+    'Relu': ('QuantizedRelu', _first(1), False, lambda n: True, ()),
+    'Relu6': ('QuantizedRelu6', _first(1), False, lambda n: True, ()),
+    'MaxPool': ('QuantizedMaxPool', _first(1), False, _pool_ok,
                 ('ksize', 'strides', 'padding')),
-    'Reshape': ('QuantizedReshape', (0,), False,
+    'AvgPool': ('QuantizedAvgPool', _first(1), False, _pool_ok,
+                ('ksize', 'strides', 'padding')),
+    'Reshape': ('QuantizedReshape', _first(1), False,
                 lambda n: _attr(n, 'Tshape', _I32) == _I32, ()),
+    'ConcatV2': ('QuantizedConcat', _concat_v2_values, False, _concat_ok,
+                 ('N',)),
+    'Concat': ('QuantizedConcat', _concat_values, False, _concat_ok, ('N',)),
 }
 
 
 def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
                    fallback_max=None):
-    """Rewrites float32 Conv2D, MatMul, BiasAdd, Relu, MaxPool and Reshape
-    (NHWC) to their quantized ops.
+    """Rewrites float32 Conv2D, MatMul, BiasAdd, Relu, Relu6, MaxPool,
+    AvgPool, Reshape, ConcatV2 and Concat (NHWC) to their quantized ops.
+
+    A node with a control input, a pool or conv that is not NHWC, and a
+    ConcatV2 with an int64 axis stay float. QuantizedConcat takes the axis
+    first (ConcatV2 has it last), then the N tensors, the N minima and the N
+    maxima; each of the N inputs gets a quantize group of its own.
 
     First pass: every such node, in isolation, becomes quantized inputs
     (activations through Reshape/Min/Max/QuantizeV2, Consts through numpy),
@@ -229,15 +259,22 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
             out.append(n)
             continue
         qop, q_inputs, is_i32, _, keep = rw
+        q_inputs = q_inputs(n)
         name, dev = n['name'], n.get('device', '')
         refs = [quantized_input(name, k, n['input'][k]) for k in q_inputs]
         ts = [triple(r) for r in refs]
-        # tensors first, then the other inputs, then the ranges in order
-        ins = [t[0] for t in ts] + n['input'][len(q_inputs):]
-        for t in ts:
-            ins += t[1:]
+        rest = [i for k, i in enumerate(n['input']) if k not in q_inputs]
+        if qop == 'QuantizedConcat':
+            # the axis moves to the front; all mins, then all maxes
+            ins = rest + [t[0] for t in ts] + [t[1] for t in ts] + \
+                [t[2] for t in ts]
+        else:
+            # tensors first, then the other inputs, then the ranges in order
+            ins = [t[0] for t in ts] + rest
+            for t in ts:
+                ins += t[1:]
         attr = {k: n['attr'][k] for k in keep if k in n['attr']}
-        if qop == 'QuantizedReshape':
+        if qop in ('QuantizedReshape', 'QuantizedConcat'):
             attr['T'] = ('type', _U8)
         last = name + '/eightbit'
         out.append(_node(last, qop, ins, attr, dev))

@@ -4,74 +4,33 @@
 #include <cmath>
 
 #include "kernels/kernel_util.h"
+#include "kernels/window_geom.h"
 
 namespace stf {
-
-struct Conv2DParams {
-  int64_t N, H, W, C, R, S, K, stride_h, stride_w, pad_h, pad_w, P, Q;
-};
-
-static Status ComputeConvParams(const TensorShape& input,
-                                const TensorShape& filter,
-                                const std::vector<int64_t>& strides,
-                                const std::string& padding, Conv2DParams* p) {
-  p->N = input.dim_size(0);
-  p->H = input.dim_size(1);
-  p->W = input.dim_size(2);
-  p->C = input.dim_size(3);
-  p->R = filter.dim_size(0);
-  p->S = filter.dim_size(1);
-  if (filter.dim_size(2) != p->C)
-    return errors::InvalidArgument("Conv2D channel mismatch");
-  p->K = filter.dim_size(3);
-  p->stride_h = strides[1];
-  p->stride_w = strides[2];
-  if (padding == "SAME") {
-    p->P = (p->H + p->stride_h - 1) / p->stride_h;
-    p->Q = (p->W + p->stride_w - 1) / p->stride_w;
-    int64_t pad_rows = std::max<int64_t>(
-        0, (p->P - 1) * p->stride_h + p->R - p->H);
-    int64_t pad_cols = std::max<int64_t>(
-        0, (p->Q - 1) * p->stride_w + p->S - p->W);
-    p->pad_h = pad_rows / 2;
-    p->pad_w = pad_cols / 2;
-  } else if (padding == "VALID") {
-    p->P = (p->H - p->R) / p->stride_h + 1;
-    p->Q = (p->W - p->S) / p->stride_w + 1;
-    p->pad_h = p->pad_w = 0;
-  } else {
-    return errors::InvalidArgument("bad padding: ", padding);
-  }
-  return Status::OK();
-}
 
 template <typename T>
 class Conv2DOp : public OpKernel {
  public:
-  explicit Conv2DOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
-    ctx->GetAttr("strides", &strides_);
-    ctx->GetAttr("padding", &padding_);
-  }
+  explicit Conv2DOp(OpKernelConstruction* ctx) : OpKernel(ctx), attrs_(ctx) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
     const Tensor& filter = ctx->input(1);
-    Conv2DParams p;
-    OP_REQUIRES_OK(ctx, ComputeConvParams(in.shape(), filter.shape(), strides_,
-                                          padding_, &p));
+    ConvGeom p;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(in.shape(), filter.shape(), attrs_, &p));
     Tensor* out = ctx->allocate_output(0, TensorShape({p.N, p.P, p.Q, p.K}));
     const T* x = in.flat<T>();
     const T* w = filter.flat<T>();
     T* y = out->flat<T>();
     std::memset(y, 0, out->TotalBytes());
     for (int64_t n = 0; n < p.N; ++n)
-      for (int64_t ph = 0; ph < p.P; ++ph)
-        for (int64_t pw = 0; pw < p.Q; ++pw) {
-          T* yrow = y + ((n * p.P + ph) * p.Q + pw) * p.K;
+      for (int64_t oh = 0; oh < p.P; ++oh)
+        for (int64_t ow = 0; ow < p.Q; ++ow) {
+          T* yrow = y + ((n * p.P + oh) * p.Q + ow) * p.K;
           for (int64_t r = 0; r < p.R; ++r) {
-            int64_t ih = ph * p.stride_h - p.pad_h + r;
+            int64_t ih = oh * p.sh - p.ph + r;
             if (ih < 0 || ih >= p.H) continue;
             for (int64_t s = 0; s < p.S; ++s) {
-              int64_t iw = pw * p.stride_w - p.pad_w + s;
+              int64_t iw = ow * p.sw - p.pw + s;
               if (iw < 0 || iw >= p.W) continue;
               const T* xrow = x + ((n * p.H + ih) * p.W + iw) * p.C;
               const T* wrow = w + (r * p.S + s) * p.C * p.K;
@@ -86,8 +45,7 @@ class Conv2DOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_CPU_KERNEL_FLOATS("Conv2D", Conv2DOp)
 
@@ -95,18 +53,14 @@ template <typename T>
 class Conv2DBackpropInputOp : public OpKernel {
  public:
   explicit Conv2DBackpropInputOp(OpKernelConstruction* ctx, bool side = false)
-      : OpKernel(ctx), side_(side) {
-    ctx->GetAttr("strides", &strides_);
-    ctx->GetAttr("padding", &padding_);
-  }
+      : OpKernel(ctx), attrs_(ctx), side_(side) {}
   void Compute(OpKernelContext* ctx) override {
     auto in_sizes = IntVector(ctx->input(0));
     const Tensor& filter = ctx->input(1);
     const Tensor& dy = ctx->input(2);
     TensorShape in_shape(in_sizes);
-    Conv2DParams p;
-    OP_REQUIRES_OK(ctx, ComputeConvParams(in_shape, filter.shape(), strides_,
-                                          padding_, &p));
+    ConvGeom p;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(in_shape, filter.shape(), attrs_, &p));
     Tensor* out = ctx->allocate_output(0, in_shape);
     const T* w = filter.flat<T>();
     const T* g = dy.flat<T>();
@@ -123,14 +77,14 @@ class Conv2DBackpropInputOp : public OpKernel {
       std::memset(dx, 0, out->TotalBytes());
     }
     for (int64_t n = 0; n < p.N; ++n)
-      for (int64_t ph = 0; ph < p.P; ++ph)
-        for (int64_t pw = 0; pw < p.Q; ++pw) {
-          const T* grow = g + ((n * p.P + ph) * p.Q + pw) * p.K;
+      for (int64_t oh = 0; oh < p.P; ++oh)
+        for (int64_t ow = 0; ow < p.Q; ++ow) {
+          const T* grow = g + ((n * p.P + oh) * p.Q + ow) * p.K;
           for (int64_t r = 0; r < p.R; ++r) {
-            int64_t ih = ph * p.stride_h - p.pad_h + r;
+            int64_t ih = oh * p.sh - p.ph + r;
             if (ih < 0 || ih >= p.H) continue;
             for (int64_t s = 0; s < p.S; ++s) {
-              int64_t iw = pw * p.stride_w - p.pad_w + s;
+              int64_t iw = ow * p.sw - p.pw + s;
               if (iw < 0 || iw >= p.W) continue;
               T* xrow = dx + ((n * p.H + ih) * p.W + iw) * p.C;
               const T* wrow = w + (r * p.S + s) * p.C * p.K;
@@ -146,8 +100,7 @@ class Conv2DBackpropInputOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
   bool side_;
 };
 REGISTER_CPU_KERNEL_FLOATS("Conv2DBackpropInput", Conv2DBackpropInputOp)
@@ -163,32 +116,29 @@ REGISTER_CPU_KERNEL_FLOATS("Conv2DBackpropInputAdd", Conv2DBackpropInputAddOp)
 template <typename T>
 class Conv2DBackpropFilterOp : public OpKernel {
  public:
-  explicit Conv2DBackpropFilterOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
-    ctx->GetAttr("strides", &strides_);
-    ctx->GetAttr("padding", &padding_);
-  }
+  explicit Conv2DBackpropFilterOp(OpKernelConstruction* ctx)
+      : OpKernel(ctx), attrs_(ctx) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
     auto f_sizes = IntVector(ctx->input(1));
     const Tensor& dy = ctx->input(2);
     TensorShape f_shape(f_sizes);
-    Conv2DParams p;
-    OP_REQUIRES_OK(
-        ctx, ComputeConvParams(in.shape(), f_shape, strides_, padding_, &p));
+    ConvGeom p;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(in.shape(), f_shape, attrs_, &p));
     Tensor* out = ctx->allocate_output(0, f_shape);
     const T* x = in.flat<T>();
     const T* g = dy.flat<T>();
     T* dw = out->flat<T>();
     std::memset(dw, 0, out->TotalBytes());
     for (int64_t n = 0; n < p.N; ++n)
-      for (int64_t ph = 0; ph < p.P; ++ph)
-        for (int64_t pw = 0; pw < p.Q; ++pw) {
-          const T* grow = g + ((n * p.P + ph) * p.Q + pw) * p.K;
+      for (int64_t oh = 0; oh < p.P; ++oh)
+        for (int64_t ow = 0; ow < p.Q; ++ow) {
+          const T* grow = g + ((n * p.P + oh) * p.Q + ow) * p.K;
           for (int64_t r = 0; r < p.R; ++r) {
-            int64_t ih = ph * p.stride_h - p.pad_h + r;
+            int64_t ih = oh * p.sh - p.ph + r;
             if (ih < 0 || ih >= p.H) continue;
             for (int64_t s = 0; s < p.S; ++s) {
-              int64_t iw = pw * p.stride_w - p.pad_w + s;
+              int64_t iw = ow * p.sw - p.pw + s;
               if (iw < 0 || iw >= p.W) continue;
               const T* xrow = x + ((n * p.H + ih) * p.W + iw) * p.C;
               T* wrow = dw + (r * p.S + s) * p.C * p.K;
@@ -203,66 +153,33 @@ class Conv2DBackpropFilterOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_CPU_KERNEL_FLOATS("Conv2DBackpropFilter", Conv2DBackpropFilterOp)
 
 // --------------------------------- pooling ---------------------------------
-struct PoolParams {
-  int64_t N, H, W, C, kh, kw, sh, sw, pad_h, pad_w, P, Q;
-};
-static PoolParams GetPoolParams(const TensorShape& input,
-                                const std::vector<int64_t>& ksize,
-                                const std::vector<int64_t>& strides,
-                                const std::string& padding) {
-  PoolParams p;
-  p.N = input.dim_size(0);
-  p.H = input.dim_size(1);
-  p.W = input.dim_size(2);
-  p.C = input.dim_size(3);
-  p.kh = ksize[1];
-  p.kw = ksize[2];
-  p.sh = strides[1];
-  p.sw = strides[2];
-  if (padding == "SAME") {
-    p.P = (p.H + p.sh - 1) / p.sh;
-    p.Q = (p.W + p.sw - 1) / p.sw;
-    p.pad_h = std::max<int64_t>(0, (p.P - 1) * p.sh + p.kh - p.H) / 2;
-    p.pad_w = std::max<int64_t>(0, (p.Q - 1) * p.sw + p.kw - p.W) / 2;
-  } else {
-    p.P = (p.H - p.kh) / p.sh + 1;
-    p.Q = (p.W - p.kw) / p.sw + 1;
-    p.pad_h = p.pad_w = 0;
-  }
-  return p;
-}
-
 template <typename T, bool is_max>
 class PoolOp : public OpKernel {
  public:
-  explicit PoolOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
-    ctx->GetAttr("ksize", &ksize_);
-    ctx->GetAttr("strides", &strides_);
-    ctx->GetAttr("padding", &padding_);
-  }
+  explicit PoolOp(OpKernelConstruction* ctx) : OpKernel(ctx), attrs_(ctx) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    PoolParams p = GetPoolParams(in.shape(), ksize_, strides_, padding_);
+    PoolGeom p;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(in.shape(), attrs_, &p));
     Tensor* out = ctx->allocate_output(0, TensorShape({p.N, p.P, p.Q, p.C}));
     const T* x = in.flat<T>();
     T* y = out->flat<T>();
     for (int64_t n = 0; n < p.N; ++n)
-      for (int64_t ph = 0; ph < p.P; ++ph)
-        for (int64_t pw = 0; pw < p.Q; ++pw)
+      for (int64_t oh = 0; oh < p.P; ++oh)
+        for (int64_t ow = 0; ow < p.Q; ++ow)
           for (int64_t c = 0; c < p.C; ++c) {
             T best = is_max ? std::numeric_limits<T>::lowest() : T(0);
             int64_t count = 0;
             for (int64_t kh = 0; kh < p.kh; ++kh) {
-              int64_t ih = ph * p.sh - p.pad_h + kh;
+              int64_t ih = oh * p.sh - p.ph + kh;
               if (ih < 0 || ih >= p.H) continue;
               for (int64_t kw = 0; kw < p.kw; ++kw) {
-                int64_t iw = pw * p.sw - p.pad_w + kw;
+                int64_t iw = ow * p.sw - p.pw + kw;
                 if (iw < 0 || iw >= p.W) continue;
                 T v = x[((n * p.H + ih) * p.W + iw) * p.C + c];
                 if (is_max) best = v > best ? v : best;
@@ -270,14 +187,13 @@ class PoolOp : public OpKernel {
                 ++count;
               }
             }
-            y[((n * p.P + ph) * p.Q + pw) * p.C + c] =
+            y[((n * p.P + oh) * p.Q + ow) * p.C + c] =
                 is_max ? best : best / (T)count;
           }
   }
 
- protected:
-  std::vector<int64_t> ksize_, strides_;
-  std::string padding_;
+ private:
+  PoolAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("MaxPool").Device(DEVICE_CPU).TypeConstraint<float>("T"), PoolOp<float, true>);
 REGISTER_KERNEL_BUILDER(Name("MaxPool").Device(DEVICE_CPU).TypeConstraint<double>("T"), PoolOp<double, true>);
@@ -287,32 +203,30 @@ REGISTER_KERNEL_BUILDER(Name("AvgPool").Device(DEVICE_CPU).TypeConstraint<double
 template <typename T>
 class MaxPoolGradOp : public OpKernel {
  public:
-  explicit MaxPoolGradOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
-    ctx->GetAttr("ksize", &ksize_);
-    ctx->GetAttr("strides", &strides_);
-    ctx->GetAttr("padding", &padding_);
-  }
+  explicit MaxPoolGradOp(OpKernelConstruction* ctx)
+      : OpKernel(ctx), attrs_(ctx) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
     const Tensor& dy = ctx->input(2);
-    PoolParams p = GetPoolParams(in.shape(), ksize_, strides_, padding_);
+    PoolGeom p;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(in.shape(), attrs_, &p));
     Tensor* out = ctx->allocate_output(0, in.shape());
     const T* x = in.flat<T>();
     const T* g = dy.flat<T>();
     T* dx = out->flat<T>();
     std::memset(dx, 0, out->TotalBytes());
     for (int64_t n = 0; n < p.N; ++n)
-      for (int64_t ph = 0; ph < p.P; ++ph)
-        for (int64_t pw = 0; pw < p.Q; ++pw)
+      for (int64_t oh = 0; oh < p.P; ++oh)
+        for (int64_t ow = 0; ow < p.Q; ++ow)
           for (int64_t c = 0; c < p.C; ++c) {
             // find argmax
             T best = std::numeric_limits<T>::lowest();
             int64_t bi = -1;
             for (int64_t kh = 0; kh < p.kh; ++kh) {
-              int64_t ih = ph * p.sh - p.pad_h + kh;
+              int64_t ih = oh * p.sh - p.ph + kh;
               if (ih < 0 || ih >= p.H) continue;
               for (int64_t kw = 0; kw < p.kw; ++kw) {
-                int64_t iw = pw * p.sw - p.pad_w + kw;
+                int64_t iw = ow * p.sw - p.pw + kw;
                 if (iw < 0 || iw >= p.W) continue;
                 int64_t idx = ((n * p.H + ih) * p.W + iw) * p.C + c;
                 if (x[idx] > best) {
@@ -321,13 +235,12 @@ class MaxPoolGradOp : public OpKernel {
                 }
               }
             }
-            if (bi >= 0) dx[bi] += g[((n * p.P + ph) * p.Q + pw) * p.C + c];
+            if (bi >= 0) dx[bi] += g[((n * p.P + oh) * p.Q + ow) * p.C + c];
           }
   }
 
  private:
-  std::vector<int64_t> ksize_, strides_;
-  std::string padding_;
+  PoolAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("MaxPoolGrad").Device(DEVICE_CPU).TypeConstraint<float>("T"), MaxPoolGradOp<float>);
 REGISTER_KERNEL_BUILDER(Name("MaxPoolGrad").Device(DEVICE_CPU).TypeConstraint<double>("T"), MaxPoolGradOp<double>);
@@ -335,40 +248,38 @@ REGISTER_KERNEL_BUILDER(Name("MaxPoolGrad").Device(DEVICE_CPU).TypeConstraint<do
 template <typename T>
 class AvgPoolGradOp : public OpKernel {
  public:
-  explicit AvgPoolGradOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
-    ctx->GetAttr("ksize", &ksize_);
-    ctx->GetAttr("strides", &strides_);
-    ctx->GetAttr("padding", &padding_);
-  }
+  explicit AvgPoolGradOp(OpKernelConstruction* ctx)
+      : OpKernel(ctx), attrs_(ctx) {}
   void Compute(OpKernelContext* ctx) override {
     auto in_sizes = IntVector(ctx->input(0));
     const Tensor& dy = ctx->input(1);
     TensorShape in_shape(in_sizes);
-    PoolParams p = GetPoolParams(in_shape, ksize_, strides_, padding_);
+    PoolGeom p;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(in_shape, attrs_, &p));
     Tensor* out = ctx->allocate_output(0, in_shape);
     const T* g = dy.flat<T>();
     T* dx = out->flat<T>();
     std::memset(dx, 0, out->TotalBytes());
     for (int64_t n = 0; n < p.N; ++n)
-      for (int64_t ph = 0; ph < p.P; ++ph)
-        for (int64_t pw = 0; pw < p.Q; ++pw) {
+      for (int64_t oh = 0; oh < p.P; ++oh)
+        for (int64_t ow = 0; ow < p.Q; ++ow) {
           // count valid positions
           int64_t count = 0;
           for (int64_t kh = 0; kh < p.kh; ++kh) {
-            int64_t ih = ph * p.sh - p.pad_h + kh;
+            int64_t ih = oh * p.sh - p.ph + kh;
             if (ih < 0 || ih >= p.H) continue;
             for (int64_t kw = 0; kw < p.kw; ++kw) {
-              int64_t iw = pw * p.sw - p.pad_w + kw;
+              int64_t iw = ow * p.sw - p.pw + kw;
               if (iw >= 0 && iw < p.W) ++count;
             }
           }
           for (int64_t c = 0; c < p.C; ++c) {
-            T gv = g[((n * p.P + ph) * p.Q + pw) * p.C + c] / (T)count;
+            T gv = g[((n * p.P + oh) * p.Q + ow) * p.C + c] / (T)count;
             for (int64_t kh = 0; kh < p.kh; ++kh) {
-              int64_t ih = ph * p.sh - p.pad_h + kh;
+              int64_t ih = oh * p.sh - p.ph + kh;
               if (ih < 0 || ih >= p.H) continue;
               for (int64_t kw = 0; kw < p.kw; ++kw) {
-                int64_t iw = pw * p.sw - p.pad_w + kw;
+                int64_t iw = ow * p.sw - p.pw + kw;
                 if (iw < 0 || iw >= p.W) continue;
                 dx[((n * p.H + ih) * p.W + iw) * p.C + c] += gv;
               }
@@ -378,8 +289,7 @@ class AvgPoolGradOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> ksize_, strides_;
-  std::string padding_;
+  PoolAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("AvgPoolGrad").Device(DEVICE_CPU).TypeConstraint<float>("T").HostMemory("orig_input_shape"), AvgPoolGradOp<float>);
 REGISTER_KERNEL_BUILDER(Name("AvgPoolGrad").Device(DEVICE_CPU).TypeConstraint<double>("T").HostMemory("orig_input_shape"), AvgPoolGradOp<double>);
@@ -500,54 +410,28 @@ REGISTER_KERNEL_BUILDER(Name("FusedBatchNormGrad").Device(DEVICE_CPU).TypeConstr
 // (reference core/kernels/depthwise_conv_op.cc; plain loops, f32 accum)
 namespace {
 
-struct DwShape {
-  int64_t N, H, W, C, R, S, sh, sw, ph, pw, P, Q, mult;
-};
-
-static Status DwShapeFrom(const TensorShape& x, const TensorShape& f,
-                          const std::vector<int64_t>& strides,
-                          const std::string& padding, DwShape* d) {
-  d->N = x.dim_size(0); d->H = x.dim_size(1); d->W = x.dim_size(2);
-  d->C = x.dim_size(3);
-  d->R = f.dim_size(0); d->S = f.dim_size(1); d->mult = f.dim_size(3);
-  d->sh = strides[1]; d->sw = strides[2];
-  if (padding == "SAME") {
-    d->P = (d->H + d->sh - 1) / d->sh;
-    d->Q = (d->W + d->sw - 1) / d->sw;
-    d->ph = std::max<int64_t>(0, (d->P - 1) * d->sh + d->R - d->H) / 2;
-    d->pw = std::max<int64_t>(0, (d->Q - 1) * d->sw + d->S - d->W) / 2;
-  } else {
-    d->P = (d->H - d->R) / d->sh + 1;
-    d->Q = (d->W - d->S) / d->sw + 1;
-    d->ph = d->pw = 0;
-  }
-  return Status::OK();
-}
-
+// d.K is the channel multiplier of the [R, S, C, mult] filter.
 template <typename T>
 class CpuDepthwiseConvOp : public OpKernel {
  public:
-  explicit CpuDepthwiseConvOp(OpKernelConstruction* c) : OpKernel(c) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+  explicit CpuDepthwiseConvOp(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& w = ctx->input(1);
-    DwShape d;
-    OP_REQUIRES_OK(ctx, DwShapeFrom(x.shape(), w.shape(), strides_,
-                                    padding_, &d));
+    ConvGeom d;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &d));
     Tensor* y = ctx->allocate_output(
-        0, TensorShape({d.N, d.P, d.Q, d.C * d.mult}));
+        0, TensorShape({d.N, d.P, d.Q, d.C * d.K}));
     const T* xp = x.flat<T>();
     const T* wp = w.flat<T>();
     T* yp = y->flat<T>();
-    int64_t CM = d.C * d.mult;
+    int64_t CM = d.C * d.K;
     for (int64_t n = 0; n < d.N; ++n)
       for (int64_t p = 0; p < d.P; ++p)
         for (int64_t q = 0; q < d.Q; ++q)
           for (int64_t c = 0; c < d.C; ++c)
-            for (int64_t m = 0; m < d.mult; ++m) {
+            for (int64_t m = 0; m < d.K; ++m) {
               float acc = 0.f;
               for (int64_t r = 0; r < d.R; ++r) {
                 int64_t ih = p * d.sh - d.ph + r;
@@ -556,16 +440,15 @@ class CpuDepthwiseConvOp : public OpKernel {
                   int64_t iw = q * d.sw - d.pw + s2;
                   if (iw < 0 || iw >= d.W) continue;
                   acc += (float)xp[((n * d.H + ih) * d.W + iw) * d.C + c] *
-                         (float)wp[((r * d.S + s2) * d.C + c) * d.mult + m];
+                         (float)wp[((r * d.S + s2) * d.C + c) * d.K + m];
                 }
               }
-              yp[((n * d.P + p) * d.Q + q) * CM + c * d.mult + m] = (T)acc;
+              yp[((n * d.P + p) * d.Q + q) * CM + c * d.K + m] = (T)acc;
             }
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNative").Device(DEVICE_CPU).TypeConstraint<float>("T"), CpuDepthwiseConvOp<float>);
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNative").Device(DEVICE_CPU).TypeConstraint<bfloat16>("T"), CpuDepthwiseConvOp<bfloat16>);

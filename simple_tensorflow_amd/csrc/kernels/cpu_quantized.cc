@@ -15,6 +15,7 @@
 #include "framework/op_kernel.h"
 #include "kernels/kernel_util.h"
 #include "kernels/quantized_util.h"
+#include "kernels/window_geom.h"
 
 namespace stf {
 namespace {
@@ -123,43 +124,18 @@ REGISTER_KERNEL_BUILDER(Name("QuantizedMatMul").Device(DEVICE_CPU),
 // output range follow QuantizedMatMul.
 class QuantizedConv2DOp : public OpKernel {
  public:
-  explicit QuantizedConv2DOp(OpKernelConstruction* c) : OpKernel(c) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+  explicit QuantizedConv2DOp(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& w = ctx->input(1);
-    OP_REQUIRES(ctx, x.dims() == 4 && w.dims() == 4,
-                errors::InvalidArgument("QuantizedConv2D needs rank-4 input "
-                                        "and filter"));
-    OP_REQUIRES(ctx, strides_.size() == 4 && strides_[0] == 1 &&
-                         strides_[3] == 1,
-                errors::InvalidArgument("QuantizedConv2D strides must be "
-                                        "[1, sh, sw, 1]"));
-    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
-                errors::InvalidArgument("QuantizedConv2D padding must be "
-                                        "SAME or VALID"));
+    ConvGeom g;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g));
     float min_x = ctx->input(2).flat<float>()[0];
     float max_x = ctx->input(3).flat<float>()[0];
     float min_w = ctx->input(4).flat<float>()[0];
     float max_w = ctx->input(5).flat<float>()[0];
-    int64_t N = x.dim_size(0), H = x.dim_size(1), W = x.dim_size(2),
-            C = x.dim_size(3);
-    int64_t R = w.dim_size(0), S = w.dim_size(1), K = w.dim_size(3);
-    OP_REQUIRES(ctx, w.dim_size(2) == C,
-                errors::InvalidArgument("conv channel mismatch"));
-    int64_t sh = strides_[1], sw = strides_[2], P, Q, ph = 0, pw = 0;
-    if (padding_ == "SAME") {
-      P = (H + sh - 1) / sh;
-      Q = (W + sw - 1) / sw;
-      ph = std::max<int64_t>(0, (P - 1) * sh + R - H) / 2;
-      pw = std::max<int64_t>(0, (Q - 1) * sw + S - W) / 2;
-    } else {
-      P = (H - R) / sh + 1;
-      Q = (W - S) / sw + 1;
-    }
-    Tensor* out = ctx->allocate_output(0, TensorShape({N, P, Q, K}));
+    Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.K}));
     const uint8_t* xp = x.flat<uint8_t>();
     const uint8_t* wp = w.flat<uint8_t>();
     int32_t* op = out->flat<int32_t>();
@@ -167,28 +143,28 @@ class QuantizedConv2DOp : public OpKernel {
     float sf = QuantStep(min_w, max_w);
     int32_t zx = QuantZeroPoint(min_x, max_x);
     int32_t zf = QuantZeroPoint(min_w, max_w);
-    std::vector<int64_t> acc(K);
-    for (int64_t n = 0; n < N; ++n)
-      for (int64_t p = 0; p < P; ++p)
-        for (int64_t q = 0; q < Q; ++q) {
+    std::vector<int64_t> acc(g.K);
+    for (int64_t n = 0; n < g.N; ++n)
+      for (int64_t p = 0; p < g.P; ++p)
+        for (int64_t q = 0; q < g.Q; ++q) {
           std::fill(acc.begin(), acc.end(), 0);
-          for (int64_t r = 0; r < R; ++r) {
-            int64_t h = p * sh - ph + r;
-            if (h < 0 || h >= H) continue;
-            for (int64_t s = 0; s < S; ++s) {
-              int64_t wi = q * sw - pw + s;
-              if (wi < 0 || wi >= W) continue;
-              const uint8_t* xr = xp + ((n * H + h) * W + wi) * C;
-              const uint8_t* wr = wp + (r * S + s) * C * K;
-              for (int64_t c = 0; c < C; ++c) {
+          for (int64_t r = 0; r < g.R; ++r) {
+            int64_t h = p * g.sh - g.ph + r;
+            if (h < 0 || h >= g.H) continue;
+            for (int64_t s = 0; s < g.S; ++s) {
+              int64_t wi = q * g.sw - g.pw + s;
+              if (wi < 0 || wi >= g.W) continue;
+              const uint8_t* xr = xp + ((n * g.H + h) * g.W + wi) * g.C;
+              const uint8_t* wr = wp + (r * g.S + s) * g.C * g.K;
+              for (int64_t c = 0; c < g.C; ++c) {
                 int64_t xv = (int32_t)xr[c] - zx;
-                for (int64_t k = 0; k < K; ++k)
-                  acc[k] += xv * ((int32_t)wr[c * K + k] - zf);
+                for (int64_t k = 0; k < g.K; ++k)
+                  acc[k] += xv * ((int32_t)wr[c * g.K + k] - zf);
               }
             }
           }
-          int32_t* o = op + ((n * P + p) * Q + q) * K;
-          for (int64_t k = 0; k < K; ++k) o[k] = (int32_t)acc[k];
+          int32_t* o = op + ((n * g.P + p) * g.Q + q) * g.K;
+          for (int64_t k = 0; k < g.K; ++k) o[k] = (int32_t)acc[k];
         }
     ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
         QuantProductMin(sx, sf);
@@ -197,8 +173,7 @@ class QuantizedConv2DOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_CPU),
                         QuantizedConv2DOp);
@@ -350,82 +325,31 @@ class QuantizedBiasAddOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("QuantizedBiasAdd").Device(DEVICE_CPU),
                         QuantizedBiasAddOp);
 
-// Attributes, argument checks and geometry (GetPoolParams of cpu_nn.cc) of
-// the two NHWC quint8 pools. Both pass their ranges through.
+// Attributes of the two NHWC quint8 pools. Both pass their ranges through.
 class QuantizedPoolOp : public OpKernel {
  public:
-  QuantizedPoolOp(OpKernelConstruction* c, const char* name)
-      : OpKernel(c), name_(name) {
-    c->GetAttr("ksize", &ksize_);
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+  explicit QuantizedPoolOp(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
 
  protected:
-  struct Geom {
-    int64_t N, H, W, C, kh, kw, sh, sw, P, Q, pad_h, pad_w;
-  };
-  // False, with the status set, when the arguments are invalid.
-  bool Geometry(OpKernelContext* ctx, const Tensor& in, Geom* g) const {
-    const char* what = nullptr;
-    if (in.dims() != 4) {
-      what = " needs rank-4 input";
-    } else if (!(ksize_.size() == 4 && strides_.size() == 4 &&
-                 ksize_[1] >= 1 && ksize_[2] >= 1 && strides_[1] >= 1 &&
-                 strides_[2] >= 1)) {
-      what = " ksize and strides must be [1, h, w, 1]";
-    } else if (padding_ != "SAME" && padding_ != "VALID") {
-      what = " padding must be SAME or VALID";
-    }
-    if (!what) {
-      g->N = in.dim_size(0);
-      g->H = in.dim_size(1);
-      g->W = in.dim_size(2);
-      g->C = in.dim_size(3);
-      g->kh = ksize_[1];
-      g->kw = ksize_[2];
-      g->sh = strides_[1];
-      g->sw = strides_[2];
-      g->pad_h = g->pad_w = 0;
-      if (padding_ == "SAME") {
-        g->P = (g->H + g->sh - 1) / g->sh;
-        g->Q = (g->W + g->sw - 1) / g->sw;
-        g->pad_h =
-            std::max<int64_t>(0, (g->P - 1) * g->sh + g->kh - g->H) / 2;
-        g->pad_w =
-            std::max<int64_t>(0, (g->Q - 1) * g->sw + g->kw - g->W) / 2;
-      } else {
-        g->P = (g->H - g->kh) / g->sh + 1;
-        g->Q = (g->W - g->kw) / g->sw + 1;
-      }
-      if (g->P < 0 || g->Q < 0) what = " window larger than the VALID input";
-    }
-    if (what) ctx->SetStatus(errors::InvalidArgument(name_, what));
-    return !what;
-  }
   void ForwardRanges(OpKernelContext* ctx) const {
     ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
         ctx->input(1).flat<float>()[0];
     ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
         ctx->input(2).flat<float>()[0];
   }
-
- private:
-  const char* name_;
-  std::vector<int64_t> ksize_, strides_;
-  std::string padding_;
+  PoolAttrs attrs_;
 };
 
 // NHWC max over the taps inside the image. The mapping is monotone, so the
 // ranges pass through.
 class QuantizedMaxPoolOp : public QuantizedPoolOp {
  public:
-  explicit QuantizedMaxPoolOp(OpKernelConstruction* c)
-      : QuantizedPoolOp(c, "QuantizedMaxPool") {}
+  using QuantizedPoolOp::QuantizedPoolOp;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    Geom g;
-    if (!Geometry(ctx, in, &g)) return;
+    PoolGeom g;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(in.shape(), attrs_, &g));
     Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.C}));
     const uint8_t* x = in.flat<uint8_t>();
     uint8_t* y = out->flat<uint8_t>();
@@ -435,10 +359,10 @@ class QuantizedMaxPoolOp : public QuantizedPoolOp {
           uint8_t* o = y + ((n * g.P + p) * g.Q + q) * g.C;
           std::fill(o, o + g.C, (uint8_t)0);
           for (int64_t r = 0; r < g.kh; ++r) {
-            int64_t ih = p * g.sh - g.pad_h + r;
+            int64_t ih = p * g.sh - g.ph + r;
             if (ih < 0 || ih >= g.H) continue;
             for (int64_t s = 0; s < g.kw; ++s) {
-              int64_t iw = q * g.sw - g.pad_w + s;
+              int64_t iw = q * g.sw - g.pw + s;
               if (iw < 0 || iw >= g.W) continue;
               const uint8_t* xr = x + ((n * g.H + ih) * g.W + iw) * g.C;
               for (int64_t c = 0; c < g.C; ++c)
@@ -458,12 +382,11 @@ REGISTER_KERNEL_BUILDER(Name("QuantizedMaxPool").Device(DEVICE_CPU),
 // [mn, mx], so the ranges pass through.
 class QuantizedAvgPoolOp : public QuantizedPoolOp {
  public:
-  explicit QuantizedAvgPoolOp(OpKernelConstruction* c)
-      : QuantizedPoolOp(c, "QuantizedAvgPool") {}
+  using QuantizedPoolOp::QuantizedPoolOp;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    Geom g;
-    if (!Geometry(ctx, in, &g)) return;
+    PoolGeom g;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(in.shape(), attrs_, &g));
     Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.C}));
     const uint8_t* x = in.flat<uint8_t>();
     uint8_t* y = out->flat<uint8_t>();
@@ -474,10 +397,10 @@ class QuantizedAvgPoolOp : public QuantizedPoolOp {
           std::fill(acc.begin(), acc.end(), 0);
           int32_t taps = 0;
           for (int64_t r = 0; r < g.kh; ++r) {
-            int64_t ih = p * g.sh - g.pad_h + r;
+            int64_t ih = p * g.sh - g.ph + r;
             if (ih < 0 || ih >= g.H) continue;
             for (int64_t s = 0; s < g.kw; ++s) {
-              int64_t iw = q * g.sw - g.pad_w + s;
+              int64_t iw = q * g.sw - g.pw + s;
               if (iw < 0 || iw >= g.W) continue;
               const uint8_t* xr = x + ((n * g.H + ih) * g.W + iw) * g.C;
               for (int64_t c = 0; c < g.C; ++c) acc[c] += xr[c];

@@ -6,10 +6,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <functional>
 
 #include "kernels/hip/stf_kernels.h"
 #include "kernels/kernel_util.h"
+#include "kernels/window_geom.h"
 
 #define GPU_STREAM(ctx) ((hipStream_t)(ctx)->device()->compute_stream())
 #define OP_HIP_OK(ctx, expr)                                              \
@@ -49,6 +51,47 @@ enum {
   B_TANH_GRAD, B_RSQRT_GRAD, B_SQRT_GRAD, B_RELU_GRAD, B_RELU6_GRAD,
   B_SOFTPLUS_GRAD
 };
+
+// Window geometry (kernels/window_geom.h) as the HIP entry points take it:
+// InvalidArgument, not truncation, where a field does not fit in int.
+inline Status FitInt(const std::string& op,
+                     std::initializer_list<int64_t> values) {
+  for (int64_t v : values)
+    if (v > INT_MAX)
+      return errors::InvalidArgument(op, ": dimension ", v,
+                                     " does not fit the GPU kernels' int");
+  return Status::OK();
+}
+inline Status ToAbi(const std::string& op, const ConvGeom& g,
+                    StfConvGeom* out) {
+  STF_RETURN_IF_ERROR(FitInt(op, {g.N, g.H, g.W, g.C, g.R, g.S, g.sh, g.sw,
+                                  g.ph, g.pw, g.P, g.Q}));
+  *out = StfConvGeom{(int)g.N,  (int)g.H,  (int)g.W,  (int)g.C,
+                     (int)g.R,  (int)g.S,  (int)g.sh, (int)g.sw,
+                     (int)g.ph, (int)g.pw, (int)g.P,  (int)g.Q, g.K};
+  return Status::OK();
+}
+inline Status ToAbi(const std::string& op, const PoolGeom& g,
+                    StfPoolGeom* out) {
+  STF_RETURN_IF_ERROR(FitInt(op, {g.N, g.H, g.W, g.C, g.kh, g.kw, g.sh, g.sw,
+                                  g.ph, g.pw, g.P, g.Q}));
+  *out = StfPoolGeom{(int)g.N,  (int)g.H,  (int)g.W,  (int)g.C,
+                     (int)g.kh, (int)g.kw, (int)g.sh, (int)g.sw,
+                     (int)g.ph, (int)g.pw, (int)g.P,  (int)g.Q};
+  return Status::OK();
+}
+// A conv's geometry both ways; the pool ops need nothing but the ABI struct.
+inline Status MakeConvGeom(const TensorShape& x, const TensorShape& filter,
+                           const ConvAttrs& a, ConvGeom* g, StfConvGeom* sg) {
+  STF_RETURN_IF_ERROR(MakeConvGeom(x, filter, a, g));
+  return ToAbi(a.op, *g, sg);
+}
+inline Status MakePoolGeom(const TensorShape& x, const PoolAttrs& a,
+                           StfPoolGeom* out) {
+  PoolGeom g;
+  STF_RETURN_IF_ERROR(MakePoolGeom(x, a, &g));
+  return ToAbi(a.op, g, out);
+}
 
 // zero an f32 device buffer on the stream
 inline hipError_t ZeroF32(void* p, int64_t n, hipStream_t s) {

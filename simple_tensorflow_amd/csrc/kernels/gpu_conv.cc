@@ -7,50 +7,6 @@ namespace {
 // ---------------------------------------------------------------------------
 // Conv2D family (implicit-GEMM, or im2col + MFMA GEMM)
 // ---------------------------------------------------------------------------
-struct GpuConvGeom {
-  int64_t N, H, W, C, R, S, K, sh, sw, ph, pw, P, Q;
-  int64_t M() const { return N * P * Q; }
-  int64_t RSC() const { return R * S * C; }
-  // K-dim padded to the GEMM K-step so glds staging stays 16B-aligned
-  // (conv1's RSC=147 would otherwise force the scalar edge path everywhere).
-  int64_t RSCp() const { return (RSC() + 63) & ~int64_t(63); }
-  bool is_1x1_s1() const {
-    return R == 1 && S == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0;
-  }
-  // the geometry as the HIP entry points take it
-  StfConvGeom abi() const {
-    return StfConvGeom{(int)N,  (int)H,  (int)W,  (int)C,  (int)R, (int)S,
-                       (int)sh, (int)sw, (int)ph, (int)pw, (int)P, (int)Q, K};
-  }
-};
-
-static Status GetConvGeom(const TensorShape& x, const TensorShape& f,
-                          const std::vector<int64_t>& strides,
-                          const std::string& padding, GpuConvGeom* g) {
-  g->N = x.dim_size(0);
-  g->H = x.dim_size(1);
-  g->W = x.dim_size(2);
-  g->C = x.dim_size(3);
-  g->R = f.dim_size(0);
-  g->S = f.dim_size(1);
-  g->K = f.dim_size(3);
-  if (f.dim_size(2) != g->C)
-    return errors::InvalidArgument("conv channel mismatch");
-  g->sh = strides[1];
-  g->sw = strides[2];
-  if (padding == "SAME") {
-    g->P = (g->H + g->sh - 1) / g->sh;
-    g->Q = (g->W + g->sw - 1) / g->sw;
-    g->ph = std::max<int64_t>(0, (g->P - 1) * g->sh + g->R - g->H) / 2;
-    g->pw = std::max<int64_t>(0, (g->Q - 1) * g->sw + g->S - g->W) / 2;
-  } else {
-    g->P = (g->H - g->R) / g->sh + 1;
-    g->Q = (g->W - g->S) / g->sw + 1;
-    g->ph = g->pw = 0;
-  }
-  return Status::OK();
-}
-
 // Implicit-GEMM conv (the reference's cuDNN implicit-GEMM slot,
 // conv_ops.cc:664): the column matrix is generated inside the GEMM's A
 // staging — no im2col kernel, no column buffer. STF_NO_IMPLICIT_CONV
@@ -62,27 +18,28 @@ static bool ImplicitConvEnabled() {
 
 // The implicit paths read 8-channel (16B) runs, so the C=3 stem is run on a
 // copy of x zero-padded to C8 = 8 channels (the padded channels contribute
-// nothing). Writes the copy to *xp and sets g->C = C8.
+// nothing). Writes the copy to *xp and sets the channels of *g and *sg to C8.
 static hipError_t PadChannels(OpKernelContext* ctx, const Tensor& x,
-                              GpuConvGeom* g, Tensor* xp, hipStream_t s) {
+                              ConvGeom* g, StfConvGeom* sg, Tensor* xp,
+                              hipStream_t s) {
   int64_t c8 = (g->C + 7) & ~7ll;
   *xp = ctx->allocate_temp(DT_BFLOAT16, TensorShape({g->N, g->H, g->W, c8}));
   hipError_t e = stf_block_pad(1, x.raw_data(), xp->raw_data(),
                                g->N * g->H * g->W, g->C, c8, s);
   g->C = c8;
+  sg->c = (int)c8;
   return e;
 }
 
 // Materialized column matrix col[M, ld] (ld >= RSC; the tail is zeroed).
 static hipError_t Im2Col(OpKernelContext* ctx, const Tensor& x,
-                         const GpuConvGeom& g, int64_t ld, Tensor* col,
-                         hipStream_t s) {
+                         const ConvGeom& g, const StfConvGeom& sg, int64_t ld,
+                         Tensor* col, hipStream_t s) {
   *col = ctx->allocate_temp(DT_BFLOAT16, TensorShape({g.M(), ld}));
   if (ld != g.RSC()) {
     hipError_t e = hipMemsetAsync(col->raw_data(), 0, g.M() * ld * 2, s);
     if (e != hipSuccess) return e;
   }
-  StfConvGeom sg = g.abi();
   return stf_im2col_bf16(x.raw_data(), col->raw_data(), &sg, ld, s);
 }
 
@@ -101,18 +58,15 @@ static hipError_t TransposeBf16(OpKernelContext* ctx, const void* src,
 class GpuConv2DOp : public OpKernel {
  public:
   explicit GpuConv2DOp(OpKernelConstruction* c, bool stats = false)
-      : OpKernel(c), stats_(stats) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+      : OpKernel(c), stats_(stats), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     hipStream_t s = GPU_STREAM(ctx);
     // ---- geometry ----
     Tensor x = ctx->input(0);
     Tensor w = ctx->input(1);
-    GpuConvGeom g;
-    OP_REQUIRES_OK(ctx, GetConvGeom(x.shape(), w.shape(), strides_, padding_,
-                                    &g));
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g, &sg));
     Tensor* y = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.K}));
     float* sums = nullptr;
     if (stats_) {
@@ -123,7 +77,7 @@ class GpuConv2DOp : public OpKernel {
       // stem: pad the channels of x and of w (zero in both)
       int64_t c = g.C;
       Tensor xp, wp;
-      OP_HIP_OK(ctx, PadChannels(ctx, x, &g, &xp, s));
+      OP_HIP_OK(ctx, PadChannels(ctx, x, &g, &sg, &xp, s));
       wp = ctx->allocate_temp(DT_BFLOAT16, TensorShape({g.RSC(), g.K}));
       OP_HIP_OK(ctx, stf_block_pad(1, w.raw_data(), wp.raw_data(), g.R * g.S,
                                    c * g.K, g.C * g.K, s));
@@ -145,7 +99,6 @@ class GpuConv2DOp : public OpKernel {
                                     s));
       w = wz;
     }
-    StfConvGeom sg = g.abi();
 
     // ---- pick the path ----
     bool fits_8ph = stf_gemm_bf16_8ph_ok(g.M(), g.K, rscp);
@@ -187,7 +140,8 @@ class GpuConv2DOp : public OpKernel {
                                        s));
     } else {
       Tensor col = x;  // 1x1/s1: x is the column matrix
-      if (!g.is_1x1_s1()) OP_HIP_OK(ctx, Im2Col(ctx, x, g, rscp, &col, s));
+      if (!g.is_1x1_s1())
+        OP_HIP_OK(ctx, Im2Col(ctx, x, g, sg, rscp, &col, s));
       if (!fits_8ph && (g.K & 7) == 0) {
         OP_HIP_OK(ctx, stf_gemm_bf16(col.raw_data(), w.raw_data(),
                                      y->raw_data(), g.M(), g.K, rscp, rscp,
@@ -217,15 +171,14 @@ class GpuConv2DOp : public OpKernel {
   }
 
  private:
-  static float* TilePartials(OpKernelContext* ctx, const GpuConvGeom& g,
+  static float* TilePartials(OpKernelContext* ctx, const ConvGeom& g,
                              Tensor* t) {
     *t = ctx->allocate_temp(DT_FLOAT, TensorShape({g.M() / 256, 2 * g.K}));
     return t->flat<float>();
   }
 
   bool stats_;
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("Conv2D").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuConv2DOp);
 
@@ -239,9 +192,7 @@ REGISTER_KERNEL_BUILDER(Name("_Conv2DBnStats").Device(DEVICE_GPU).TypeConstraint
 class GpuConv2DBackpropInputOp : public OpKernel {
  public:
   explicit GpuConv2DBackpropInputOp(OpKernelConstruction* c, bool side = false)
-      : OpKernel(c), side_(side) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
+      : OpKernel(c), attrs_(c), side_(side) {
     // STF_NO_IMPLICIT_DX (A/B runs) sends every dx back through GEMM +
     // col2im. Read per kernel, so a new graph sees a changed setting.
     implicit_dx_ = getenv("STF_NO_IMPLICIT_DX") == nullptr;
@@ -252,9 +203,9 @@ class GpuConv2DBackpropInputOp : public OpKernel {
     const Tensor& dy = ctx->input(2);
     hipStream_t s = GPU_STREAM(ctx);
     TensorShape x_shape(in_sizes);
-    GpuConvGeom g;
-    OP_REQUIRES_OK(ctx, GetConvGeom(x_shape, w.shape(), strides_, padding_,
-                                    &g));
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x_shape, w.shape(), attrs_, &g, &sg));
     Tensor* dx = ctx->allocate_output(0, x_shape);
     const void* side = nullptr;
     if (side_) {
@@ -278,7 +229,6 @@ class GpuConv2DBackpropInputOp : public OpKernel {
     // and the R*S-times-wider dcol is never written or read back. Shapes
     // outside the 8-phase gate keep GEMM + col2im: through the general NT
     // template the implicit dx measured 3% slower end to end on Inception v3.
-    StfConvGeom sg = g.abi();
     int64_t nhw = g.N * g.H * g.W;
     int64_t rskp = (g.R * g.S * g.K + 63) & ~int64_t(63);
     bool implicit = implicit_dx_ && g.sh == 1 && g.sw == 1 &&
@@ -312,8 +262,7 @@ class GpuConv2DBackpropInputOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
   bool side_;
   bool implicit_dx_;
 };
@@ -329,10 +278,8 @@ REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropInputAdd").Device(DEVICE_GPU).TypeCo
 // dW[RSC, K] = col[M, RSC]^T x dy[M, K], contraction over the output pixels.
 class GpuConv2DBackpropFilterOp : public OpKernel {
  public:
-  explicit GpuConv2DBackpropFilterOp(OpKernelConstruction* c) : OpKernel(c) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+  explicit GpuConv2DBackpropFilterOp(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     hipStream_t s = GPU_STREAM(ctx);
     // ---- geometry ----
@@ -340,9 +287,9 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
     auto f_sizes = IntVector(ctx->input(1));
     const Tensor& dy = ctx->input(2);
     TensorShape f_shape(f_sizes);
-    GpuConvGeom g;
-    OP_REQUIRES_OK(ctx, GetConvGeom(x.shape(), f_shape, strides_, padding_,
-                                    &g));
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), f_shape, attrs_, &g, &sg));
     Tensor* dw = ctx->allocate_output(0, f_shape);
     int64_t rsc = g.RSC();
 
@@ -366,21 +313,21 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
     if (path == kImplicit) {
       // Stem: run at C8 on a channel-padded x into a [R*S*C8, K] temp, then
       // drop the padded filter rows (their gradient is exactly zero).
-      GpuConvGeom gi = g;
+      ConvGeom gi = g;
+      StfConvGeom si = sg;
       Tensor xp, dwp;
       const void* xdata = x.raw_data();
       void* out = dw->raw_data();
       if (pad_c) {
-        OP_HIP_OK(ctx, PadChannels(ctx, x, &gi, &xp, s));
+        OP_HIP_OK(ctx, PadChannels(ctx, x, &gi, &si, &xp, s));
         dwp = ctx->allocate_temp(DT_BFLOAT16, TensorShape({gi.RSC(), g.K}));
         xdata = xp.raw_data();
         out = dwp.raw_data();
       }
-      StfConvGeom sg = gi.abi();
       int sk = PickSplitK(gi.RSC(), g.K, g.M());
       OP_HIP_OK(ctx, SplitKInto(ctx, gi.RSC() * g.K, [&](float* acc) {
         return stf_conv2d_dw_splitk(xdata, dy.raw_data(), acc, ZeroPage(),
-                                    &sg, sk, s);
+                                    &si, sk, s);
       }, out));
       if (pad_c)
         OP_HIP_OK(ctx, stf_block_pad(1, dwp.raw_data(), dw->raw_data(),
@@ -392,7 +339,7 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
       int64_t lda = g.C;
       if (!g.is_1x1_s1()) {
         lda = g.RSCp();
-        OP_HIP_OK(ctx, Im2Col(ctx, x, g, lda, &col, s));
+        OP_HIP_OK(ctx, Im2Col(ctx, x, g, sg, lda, &col, s));
       }
       OP_HIP_OK(ctx, GemmBf16AutoEx(ctx, col.raw_data(), dy.raw_data(),
                                     dw->raw_data(), rsc, g.K, g.M(), lda,
@@ -400,7 +347,7 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
       return;
     }
     Tensor col = x, colT, dyT;
-    if (!g.is_1x1_s1()) OP_HIP_OK(ctx, Im2Col(ctx, x, g, rsc, &col, s));
+    if (!g.is_1x1_s1()) OP_HIP_OK(ctx, Im2Col(ctx, x, g, sg, rsc, &col, s));
     OP_HIP_OK(ctx, TransposeBf16(ctx, col.raw_data(), g.M(), rsc, &colT, s));
     OP_HIP_OK(ctx, TransposeBf16(ctx, dy.raw_data(), g.M(), g.K, &dyT, s));
     OP_HIP_OK(ctx, GemmBf16AutoEx(ctx, colT.raw_data(), dyT.raw_data(),
@@ -409,101 +356,87 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropFilter").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("filter_sizes"), GpuConv2DBackpropFilterOp);
 
 // ---------------------------------------------------------------------------
-// depthwise conv (reference depthwise_conv_op_gpu.cu.cc family)
+// depthwise conv (reference depthwise_conv_op_gpu.cu.cc family); g.K is the
+// channel multiplier of the [R, S, C, mult] filter
 // ---------------------------------------------------------------------------
 class GpuDepthwiseConvOp : public OpKernel {
  public:
-  explicit GpuDepthwiseConvOp(OpKernelConstruction* c) : OpKernel(c) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+  explicit GpuDepthwiseConvOp(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
-    const Tensor& w = ctx->input(1);  // [R, S, C, mult]
-    GpuConvGeom g;
-    OP_REQUIRES_OK(ctx, GetConvGeom(x.shape(), w.shape(), strides_, padding_,
-                                    &g));
-    int mult = (int)w.dim_size(3);
+    const Tensor& w = ctx->input(1);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitInt(attrs_.op, {g.K}));  // passed as int mult
     Tensor* y = ctx->allocate_output(
-        0, TensorShape({g.N, g.P, g.Q, g.C * mult}));
-    StfConvGeom sg = g.abi();
+        0, TensorShape({g.N, g.P, g.Q, g.C * g.K}));
     OP_HIP_OK(ctx, stf_depthwise_fwd(x.raw_data(), w.raw_data(), y->raw_data(),
-                                     &sg, mult, GPU_STREAM(ctx)));
+                                     &sg, (int)g.K, GPU_STREAM(ctx)));
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNative").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuDepthwiseConvOp);
 
 class GpuDepthwiseConvBackpropInputOp : public OpKernel {
  public:
   explicit GpuDepthwiseConvBackpropInputOp(OpKernelConstruction* c)
-      : OpKernel(c) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+      : OpKernel(c), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     auto in_sizes = IntVector(ctx->input(0));
     const Tensor& w = ctx->input(1);
     const Tensor& dy = ctx->input(2);
     TensorShape x_shape(in_sizes);
-    GpuConvGeom g;
-    OP_REQUIRES_OK(ctx, GetConvGeom(x_shape, w.shape(), strides_, padding_,
-                                    &g));
-    int mult = (int)w.dim_size(3);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x_shape, w.shape(), attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitInt(attrs_.op, {g.K}));
     Tensor* dx = ctx->allocate_output(0, x_shape);
-    StfConvGeom sg = g.abi();
     OP_HIP_OK(ctx, stf_depthwise_bwd_input(dy.raw_data(), w.raw_data(),
-                                           dx->raw_data(), &sg, mult,
+                                           dx->raw_data(), &sg, (int)g.K,
                                            GPU_STREAM(ctx)));
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropInput").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("input_sizes"), GpuDepthwiseConvBackpropInputOp);
 
 class GpuDepthwiseConvBackpropFilterOp : public OpKernel {
  public:
   explicit GpuDepthwiseConvBackpropFilterOp(OpKernelConstruction* c)
-      : OpKernel(c) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+      : OpKernel(c), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     auto f_sizes = IntVector(ctx->input(1));
     const Tensor& dy = ctx->input(2);
     TensorShape f_shape(f_sizes);
-    GpuConvGeom g;
-    OP_REQUIRES_OK(ctx, GetConvGeom(x.shape(), f_shape, strides_, padding_,
-                                    &g));
-    int mult = (int)f_shape.dim_size(3);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), f_shape, attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitInt(attrs_.op, {g.K}));
     hipStream_t s = GPU_STREAM(ctx);
     Tensor* dw = ctx->allocate_output(0, f_shape);
     Tensor scratch = ctx->allocate_temp(
         DT_FLOAT, TensorShape({f_shape.num_elements()}));
     OP_HIP_OK(ctx, ZeroF32(scratch.raw_data(), f_shape.num_elements(), s));
-    StfConvGeom sg = g.abi();
     OP_HIP_OK(ctx, stf_depthwise_bwd_filter(x.raw_data(), dy.raw_data(),
-                                            scratch.flat<float>(), &sg, mult,
-                                            s));
+                                            scratch.flat<float>(), &sg,
+                                            (int)g.K, s));
     OP_HIP_OK(ctx, stf_cast(0, CastCode(dw->dtype()), scratch.raw_data(),
                             dw->raw_data(), f_shape.num_elements(), s));
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropFilter").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("filter_sizes"), GpuDepthwiseConvBackpropFilterOp);
 

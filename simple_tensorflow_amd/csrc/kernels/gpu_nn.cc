@@ -307,48 +307,14 @@ REGISTER_KERNEL_BUILDER(Name("BatchNormMiGrad").Device(DEVICE_GPU).TypeConstrain
 // ---------------------------------------------------------------------------
 // pooling
 // ---------------------------------------------------------------------------
-struct PoolAttrs {
-  std::vector<int64_t> ksize, strides;
-  std::string padding;
-};
-static void GetPool(OpKernelConstruction* c, PoolAttrs* p) {
-  c->GetAttr("ksize", &p->ksize);
-  c->GetAttr("strides", &p->strides);
-  c->GetAttr("padding", &p->padding);
-}
-// Geometry of pooling an NHWC input of shape x, as the HIP entries take it.
-static StfPoolGeom PoolGeomFor(const TensorShape& x, const PoolAttrs& p) {
-  StfPoolGeom g;
-  g.N = (int)x.dim_size(0);
-  g.H = (int)x.dim_size(1);
-  g.W = (int)x.dim_size(2);
-  g.C = (int)x.dim_size(3);
-  g.kh = (int)p.ksize[1];
-  g.kw = (int)p.ksize[2];
-  g.sh = (int)p.strides[1];
-  g.sw = (int)p.strides[2];
-  if (p.padding == "SAME") {
-    g.P = (g.H + g.sh - 1) / g.sh;
-    g.Q = (g.W + g.sw - 1) / g.sw;
-    g.ph = std::max(0, (g.P - 1) * g.sh + g.kh - g.H) / 2;
-    g.pw = std::max(0, (g.Q - 1) * g.sw + g.kw - g.W) / 2;
-  } else {
-    g.P = (g.H - g.kh) / g.sh + 1;
-    g.Q = (g.W - g.kw) / g.sw + 1;
-    g.ph = g.pw = 0;
-  }
-  return g;
-}
-
 class GpuPoolOp : public OpKernel {
  public:
   GpuPoolOp(OpKernelConstruction* c, bool is_max)
-      : OpKernel(c), is_max_(is_max) {
-    GetPool(c, &p_);
-  }
+      : OpKernel(c), is_max_(is_max), p_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
-    StfPoolGeom g = PoolGeomFor(x.shape(), p_);
+    StfPoolGeom g;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(x.shape(), p_, &g));
     Tensor* y = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.C}));
     OP_HIP_OK(ctx, stf_pool_fwd(DtypeCode(x.dtype()), is_max_, x.raw_data(),
                                 y->raw_data(), &g, GPU_STREAM(ctx)));
@@ -373,13 +339,12 @@ REGISTER_KERNEL_BUILDER(Name("AvgPool").Device(DEVICE_GPU).TypeConstraint<bfloat
 
 class GpuMaxPoolGradOp : public OpKernel {
  public:
-  explicit GpuMaxPoolGradOp(OpKernelConstruction* c) : OpKernel(c) {
-    GetPool(c, &p_);
-  }
+  explicit GpuMaxPoolGradOp(OpKernelConstruction* c) : OpKernel(c), p_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& dy = ctx->input(2);
-    StfPoolGeom g = PoolGeomFor(x.shape(), p_);
+    StfPoolGeom g;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(x.shape(), p_, &g));
     Tensor* dx = ctx->allocate_output(0, x.shape());
     hipStream_t s = GPU_STREAM(ctx);
     if (x.dtype() == DT_BFLOAT16 && g.C % 8 == 0) {
@@ -405,14 +370,13 @@ REGISTER_KERNEL_BUILDER(Name("MaxPoolGrad").Device(DEVICE_GPU).TypeConstraint<bf
 
 class GpuAvgPoolGradOp : public OpKernel {
  public:
-  explicit GpuAvgPoolGradOp(OpKernelConstruction* c) : OpKernel(c) {
-    GetPool(c, &p_);
-  }
+  explicit GpuAvgPoolGradOp(OpKernelConstruction* c) : OpKernel(c), p_(c) {}
   void Compute(OpKernelContext* ctx) override {
     auto in_sizes = IntVector(ctx->input(0));
     const Tensor& dy = ctx->input(1);
     TensorShape x_shape(in_sizes);
-    StfPoolGeom g = PoolGeomFor(x_shape, p_);
+    StfPoolGeom g;
+    OP_REQUIRES_OK(ctx, MakePoolGeom(x_shape, p_, &g));
     Tensor* dx = ctx->allocate_output(0, x_shape);
     OP_HIP_OK(ctx, stf_avg_pool_bwd(DtypeCode(dy.dtype()), dy.raw_data(),
                                     dx->raw_data(), &g, GPU_STREAM(ctx)));

@@ -124,51 +124,20 @@ REGISTER_KERNEL_BUILDER(Name("QuantizedMatMul").Device(DEVICE_GPU),
 
 class GpuQuantizedConv2DOp : public OpKernel {
  public:
-  explicit GpuQuantizedConv2DOp(OpKernelConstruction* c) : OpKernel(c) {
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+  explicit GpuQuantizedConv2DOp(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& w = ctx->input(1);
     hipStream_t s = GPU_STREAM(ctx);
-    OP_REQUIRES(ctx, x.dims() == 4 && w.dims() == 4,
-                errors::InvalidArgument("QuantizedConv2D needs rank-4 input "
-                                        "and filter"));
-    OP_REQUIRES(ctx, strides_.size() == 4 && strides_[0] == 1 &&
-                         strides_[3] == 1,
-                errors::InvalidArgument("QuantizedConv2D strides must be "
-                                        "[1, sh, sw, 1]"));
-    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
-                errors::InvalidArgument("QuantizedConv2D padding must be "
-                                        "SAME or VALID"));
-    OP_REQUIRES(ctx, w.dim_size(2) == x.dim_size(3),
-                errors::InvalidArgument("conv channel mismatch"));
+    ConvGeom cg;
     StfConvGeom g;
-    g.n = (int)x.dim_size(0);
-    g.h = (int)x.dim_size(1);
-    g.w = (int)x.dim_size(2);
-    g.c = (int)x.dim_size(3);
-    g.r = (int)w.dim_size(0);
-    g.s = (int)w.dim_size(1);
-    g.cout = w.dim_size(3);
-    g.sh = (int)strides_[1];
-    g.sw = (int)strides_[2];
-    if (padding_ == "SAME") {
-      g.p = (g.h + g.sh - 1) / g.sh;
-      g.q = (g.w + g.sw - 1) / g.sw;
-      g.ph = std::max(0, (g.p - 1) * g.sh + g.r - g.h) / 2;
-      g.pw = std::max(0, (g.q - 1) * g.sw + g.s - g.w) / 2;
-    } else {
-      g.p = (g.h - g.r) / g.sh + 1;
-      g.q = (g.w - g.s) / g.sw + 1;
-      g.ph = g.pw = 0;
-    }
-    Tensor* y = ctx->allocate_output(
-        0, TensorShape({(int64_t)g.n, (int64_t)g.p, (int64_t)g.q, g.cout}));
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &cg, &g));
+    Tensor* y = ctx->allocate_output(0,
+                                     TensorShape({cg.N, cg.P, cg.Q, cg.K}));
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
-    int64_t rsc = (int64_t)g.r * g.s * g.c;
+    int64_t rsc = cg.RSC();
     // filter [rsc, cout] -> [cout][Kp] s8 with the per-tap sums
     Tensor wp, wsums;
     OP_HIP_OK(ctx, Pack(ctx, w.raw_data(), 1, g.cout, g.cout, rsc,
@@ -179,8 +148,7 @@ class GpuQuantizedConv2DOp : public OpKernel {
     if (!implicit) {
       // small-channel stems: materialized s8 column matrix
       int64_t kp = RoundUp64(rsc);
-      col = ctx->allocate_temp(
-          DT_UINT8, TensorShape({(int64_t)g.n * g.p * g.q, kp}));
+      col = ctx->allocate_temp(DT_UINT8, TensorShape({cg.M(), kp}));
       OP_HIP_OK(ctx, stf_im2col_i8(x.raw_data(), col.raw_data(), &g, kp, s));
       ap = col.raw_data();
     }
@@ -192,8 +160,7 @@ class GpuQuantizedConv2DOp : public OpKernel {
   }
 
  private:
-  std::vector<int64_t> strides_;
-  std::string padding_;
+  ConvAttrs attrs_;
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_GPU),
                         GpuQuantizedConv2DOp);
@@ -296,8 +263,8 @@ class GpuQuantizedBiasAddOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("QuantizedBiasAdd").Device(DEVICE_GPU),
                         GpuQuantizedBiasAddOp);
 
-// QuantizedMaxPool and QuantizedAvgPool: the same attributes, checks and
-// geometry in front of two entry points of one signature.
+// QuantizedMaxPool and QuantizedAvgPool: the same attributes and geometry in
+// front of two entry points of one signature.
 using QuantizedPoolFn = hipError_t (*)(const uint8_t*, const float*,
                                        const float*, uint8_t*, float*,
                                        float*, const StfPoolGeom*,
@@ -305,50 +272,13 @@ using QuantizedPoolFn = hipError_t (*)(const uint8_t*, const float*,
 
 class GpuQuantizedPoolOp : public OpKernel {
  public:
-  GpuQuantizedPoolOp(OpKernelConstruction* c, const char* name,
-                     QuantizedPoolFn fn)
-      : OpKernel(c), name_(name), fn_(fn) {
-    c->GetAttr("ksize", &ksize_);
-    c->GetAttr("strides", &strides_);
-    c->GetAttr("padding", &padding_);
-  }
+  GpuQuantizedPoolOp(OpKernelConstruction* c, QuantizedPoolFn fn)
+      : OpKernel(c), fn_(fn), attrs_(c) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
-    OP_REQUIRES(ctx, x.dims() == 4,
-                errors::InvalidArgument(name_, " needs rank-4 input"));
-    OP_REQUIRES(ctx, ksize_.size() == 4 && strides_.size() == 4 &&
-                         ksize_[1] >= 1 && ksize_[2] >= 1 &&
-                         strides_[1] >= 1 && strides_[2] >= 1,
-                errors::InvalidArgument(name_, " ksize and strides must be "
-                                               "[1, h, w, 1]"));
-    OP_REQUIRES(ctx, padding_ == "SAME" || padding_ == "VALID",
-                errors::InvalidArgument(name_, " padding must be SAME or "
-                                               "VALID"));
     StfPoolGeom g;
-    g.N = (int)x.dim_size(0);
-    g.H = (int)x.dim_size(1);
-    g.W = (int)x.dim_size(2);
-    g.C = (int)x.dim_size(3);
-    g.kh = (int)ksize_[1];
-    g.kw = (int)ksize_[2];
-    g.sh = (int)strides_[1];
-    g.sw = (int)strides_[2];
-    if (padding_ == "SAME") {
-      g.P = (g.H + g.sh - 1) / g.sh;
-      g.Q = (g.W + g.sw - 1) / g.sw;
-      g.ph = std::max(0, (g.P - 1) * g.sh + g.kh - g.H) / 2;
-      g.pw = std::max(0, (g.Q - 1) * g.sw + g.kw - g.W) / 2;
-    } else {
-      g.P = (g.H - g.kh) / g.sh + 1;
-      g.Q = (g.W - g.kw) / g.sw + 1;
-      g.ph = g.pw = 0;
-    }
-    OP_REQUIRES(ctx, g.P >= 0 && g.Q >= 0,
-                errors::InvalidArgument(name_, " window larger than the "
-                                               "VALID input"));
-    Tensor* y = ctx->allocate_output(
-        0, TensorShape({(int64_t)g.N, (int64_t)g.P, (int64_t)g.Q,
-                        (int64_t)g.C}));
+    OP_REQUIRES_OK(ctx, MakePoolGeom(x.shape(), attrs_, &g));
+    Tensor* y = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.C}));
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
     OP_HIP_OK(ctx, fn_((const uint8_t*)x.raw_data(), F32(ctx->input(1)),
@@ -357,20 +287,18 @@ class GpuQuantizedPoolOp : public OpKernel {
   }
 
  private:
-  const char* name_;
   QuantizedPoolFn fn_;
-  std::vector<int64_t> ksize_, strides_;
-  std::string padding_;
+  PoolAttrs attrs_;
 };
 class GpuQuantizedMaxPoolOp : public GpuQuantizedPoolOp {
  public:
   explicit GpuQuantizedMaxPoolOp(OpKernelConstruction* c)
-      : GpuQuantizedPoolOp(c, "QuantizedMaxPool", stf_quantized_max_pool) {}
+      : GpuQuantizedPoolOp(c, stf_quantized_max_pool) {}
 };
 class GpuQuantizedAvgPoolOp : public GpuQuantizedPoolOp {
  public:
   explicit GpuQuantizedAvgPoolOp(OpKernelConstruction* c)
-      : GpuQuantizedPoolOp(c, "QuantizedAvgPool", stf_quantized_avg_pool) {}
+      : GpuQuantizedPoolOp(c, stf_quantized_avg_pool) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedMaxPool").Device(DEVICE_GPU),
                         GpuQuantizedMaxPoolOp);

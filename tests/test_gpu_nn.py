@@ -36,6 +36,7 @@ import simple_tensorflow_amd as tf
 from simple_tensorflow_amd.python.framework.ops import apply_op
 
 from test_gpu_kernels import _bf16, _sess
+from test_window_geom import reject_list, rejected_op, window_op
 
 pytestmark = pytest.mark.gpu
 
@@ -843,6 +844,70 @@ def test_depthwise(sess, xshape, filt, stride, padding):
     refs = _depthwise_ref(x, w, dy, g)
     for name, out, (ref, ref_abs) in zip(('y', 'dx', 'dw'), outs, refs):
         _check_bf16_sum('depthwise ' + name, out, ref, ref_abs)
+
+
+# ---------------------------------------------------------------------------
+# window geometry (csrc/kernels/window_geom.h) in front of the GPU kernels
+# ---------------------------------------------------------------------------
+def test_window_geometry(sess):
+    """The GPU MaxPool, Conv2D (bf16) and QuantizedMaxPool refuse what the
+    CPU kernels refuse (tests/test_window_geom.py), in the host op and so
+    before any launch. One MaxPool and one Conv2D with odd SAME padding (5x5,
+    window 3, stride 2) then agree with the CPU kernels: max pool exactly,
+    the conv within the bf16 sum bound of this file, its CPU result and the
+    CPU conv of the absolute values standing in for the float64 sums."""
+    gpu_ops = ('MaxPool', 'Conv2D', 'QuantizedMaxPool')
+    # A failed run leaves no trace to read the placement from, and a node
+    # without a GPU kernel falls back to the CPU, whose kernels raise the
+    # same text. Placement looks at the op, its types and the requested
+    # device only, never at ksize, strides or padding: the valid twin of
+    # each rejected node, built the same way, has to run on the GPU.
+    for op in gpu_ops:
+        twin, feeds = window_op(op, (1, 2, 2, 8), 2, [1, 2, 2, 1],
+                                [1, 1, 1, 1], 'SAME', '/gpu:0',
+                                bf16=op == 'Conv2D')
+        out, on_gpu = _trace_run(sess, twin, feeds)
+        assert twin.op.name in on_gpu, (op, sorted(on_gpu))
+        assert out.shape[:3] == (1, 2, 2), (op, out.shape)
+    # a session of its own, on the module's graph: the failed runs must not
+    # be the shared session's
+    with _sess() as s:
+        for op, case in reject_list(gpu_ops):
+            fetch, feeds = rejected_op(op, case, '/gpu:0', n=1, c=8,
+                                       bf16=op == 'Conv2D')
+            with pytest.raises(tf.errors.InvalidArgumentError,
+                               match=op + ': '):
+                s.run(fetch, feeds)
+
+    rng = np.random.RandomState(118)
+    x = _bf16(rng.randn(2, 5, 5, 8) * 0.5)
+    w = _bf16(rng.randn(3, 3, 8, 8) * 0.5)
+    pool = _pool_attrs((3, 3), (2, 2), 'SAME')
+    conv = dict(strides=[1, 2, 2, 1], padding='SAME')
+    feeds = {}
+    xf, wf = _feed(feeds, x, tf.float32), _feed(feeds, w, tf.float32)
+    xa, wa = _feed(feeds, np.abs(x), tf.float32), \
+        _feed(feeds, np.abs(w), tf.float32)
+    with tf.device('/gpu:0'):
+        fetches = [
+            apply_op('MaxPool', xf, name='g_maxpool', **pool),
+            apply_op('MaxPool', tf.cast(xf, tf.bfloat16), name='g_maxpool_bf',
+                     **pool),
+            apply_op('Conv2D', tf.cast(xf, tf.bfloat16),
+                     tf.cast(wf, tf.bfloat16), name='g_conv', **conv)]
+    with tf.device('/cpu:0'):
+        fetches += [apply_op('MaxPool', xf, **pool),
+                    apply_op('Conv2D', xf, wf, **conv),
+                    apply_op('Conv2D', xa, wa, **conv)]
+    outs, on_gpu = _trace_run(sess, fetches, feeds)
+    for name in ('g_maxpool', 'g_maxpool_bf', 'g_conv'):
+        assert name in on_gpu, (name, sorted(on_gpu))
+    pool_f32, pool_bf16, conv_bf16, pool_cpu, conv_cpu, conv_abs = outs
+    assert pool_cpu.shape == (2, 3, 3, 8) and conv_cpu.shape == (2, 3, 3, 8)
+    _exact('max pool f32 vs cpu', pool_f32, pool_cpu)
+    _exact('max pool bf16 vs cpu', pool_bf16, pool_cpu)
+    _check_bf16_sum('conv2d bf16 vs cpu', conv_bf16,
+                    conv_cpu.astype(np.float64), conv_abs.astype(np.float64))
 
 
 # ---------------------------------------------------------------------------

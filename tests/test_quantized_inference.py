@@ -117,7 +117,7 @@ def np_bias_add(xq, bq, min_x, max_x, min_b, max_b):
 
 
 def _out_dim(size, k, stride, padding):
-    """(output size, leading padding) as GetPoolParams of cpu_nn.cc."""
+    """(output size, leading padding) as WindowOutput of window_geom.h."""
     if padding == 'SAME':
         o = (size + stride - 1) // stride
         return o, max(0, (o - 1) * stride + k - size) // 2

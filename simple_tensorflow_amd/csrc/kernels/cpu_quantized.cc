@@ -5,7 +5,10 @@
 // Requantize, QuantizedBiasAdd, QuantizedMaxPool and QuantizedReshape carry
 // a quantize_nodes graph (python/tools/quantize_graph_lib.py) from the conv
 // or matmul to the next one. These kernels are the specification that
-// kernels/hip/quantized.hip reproduces bit for bit.
+// kernels/hip/quantized.hip reproduces bit for bit: the per-element formulas
+// are defined once, in kernels/quantized_util.h, and called from both; the
+// shape checks shared with kernels/gpu_quantized.cc are in
+// kernels/quantized_shapes.h.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -14,11 +17,23 @@
 
 #include "framework/op_kernel.h"
 #include "kernels/kernel_util.h"
+#include "kernels/quantized_shapes.h"
 #include "kernels/quantized_util.h"
 #include "kernels/window_geom.h"
 
 namespace stf {
 namespace {
+
+// The scalar range input i.
+float RangeIn(OpKernelContext* ctx, int i) {
+  return ctx->input(i).flat<float>()[0];
+}
+
+// Writes an output range to the scalar outputs i and i + 1.
+void RangeOut(OpKernelContext* ctx, int i, float mn, float mx) {
+  ctx->allocate_output(i, TensorShape({}))->flat<float>()[0] = mn;
+  ctx->allocate_output(i + 1, TensorShape({}))->flat<float>()[0] = mx;
+}
 
 // MIN_COMBINED: q = round((x - min) / range * 255); x = min + q * range/255.
 class QuantizeV2Op : public OpKernel {
@@ -26,19 +41,16 @@ class QuantizeV2Op : public OpKernel {
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    float mn = ctx->input(1).flat<float>()[0];
-    float mx = ctx->input(2).flat<float>()[0];
+    float mn = RangeIn(ctx, 1);
+    float mx = RangeIn(ctx, 2);
     if (mx <= mn) mx = mn + 1e-6f;
     Tensor* out = ctx->allocate_output(0, in.shape());
     float scale = 255.f / (mx - mn);
     const float* p = in.flat<float>();
     uint8_t* o = out->flat<uint8_t>();
-    for (int64_t i = 0; i < in.NumElements(); ++i) {
-      float q = std::round((p[i] - mn) * scale);
-      o[i] = (uint8_t)std::min(255.f, std::max(0.f, q));
-    }
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = mn;
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = mx;
+    for (int64_t i = 0; i < in.NumElements(); ++i)
+      o[i] = QuantizeU8(p[i], mn, scale);
+    RangeOut(ctx, 1, mn, mx);
   }
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizeV2").Device(DEVICE_CPU), QuantizeV2Op);
@@ -48,20 +60,20 @@ class DequantizeOp : public OpKernel {
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    float mn = ctx->input(1).flat<float>()[0];
-    float mx = ctx->input(2).flat<float>()[0];
+    float mn = RangeIn(ctx, 1);
+    float mx = RangeIn(ctx, 2);
     Tensor* out = ctx->allocate_output(0, in.shape());
     float* o = out->flat<float>();
     if (in.dtype() == DT_UINT8) {
       float step = QuantStep(mn, mx);
       const uint8_t* p = in.flat<uint8_t>();
       for (int64_t i = 0; i < in.NumElements(); ++i)
-        o[i] = mn + p[i] * step;
+        o[i] = DequantizeU8(p[i], mn, step);
     } else {  // qint32 carrier: min/max map the full int32 range
       const int32_t* p = in.flat<int32_t>();
-      double scale = ((double)mx - mn) / 4294967295.0;
+      double scale = QuantUnitI32(mn, mx);
       for (int64_t i = 0; i < in.NumElements(); ++i)
-        o[i] = (float)(((double)p[i] + 2147483648.0) * scale + mn);
+        o[i] = DequantizeI32(p[i], scale, mn);
     }
   }
 };
@@ -79,13 +91,13 @@ class QuantizedMatMulOp : public OpKernel {
   void Compute(OpKernelContext* ctx) override {
     const Tensor& a = ctx->input(0);
     const Tensor& b = ctx->input(1);
-    float min_a = ctx->input(2).flat<float>()[0];
-    float max_a = ctx->input(3).flat<float>()[0];
-    float min_b = ctx->input(4).flat<float>()[0];
-    float max_b = ctx->input(5).flat<float>()[0];
-    int64_t M = ta_ ? a.dim_size(1) : a.dim_size(0);
-    int64_t K = ta_ ? a.dim_size(0) : a.dim_size(1);
-    int64_t N = tb_ ? b.dim_size(0) : b.dim_size(1);
+    float min_a = RangeIn(ctx, 2);
+    float max_a = RangeIn(ctx, 3);
+    float min_b = RangeIn(ctx, 4);
+    float max_b = RangeIn(ctx, 5);
+    int64_t M, N, K;
+    OP_REQUIRES_OK(ctx,
+                   QuantMatMulDims(a.shape(), b.shape(), ta_, tb_, &M, &N, &K));
     Tensor* out = ctx->allocate_output(0, TensorShape({M, N}));
     const uint8_t* ap = a.flat<uint8_t>();
     const uint8_t* bp = b.flat<uint8_t>();
@@ -106,10 +118,7 @@ class QuantizedMatMulOp : public OpKernel {
         op[m * N + n] = (int32_t)acc;
       }
     // float value of one output unit = sa * sb; int32 range maps to:
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
-        QuantProductMin(sa, sb);
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
-        QuantProductMax(sa, sb);
+    RangeOut(ctx, 1, QuantProductMin(sa, sb), QuantProductMax(sa, sb));
   }
 
  private:
@@ -131,10 +140,10 @@ class QuantizedConv2DOp : public OpKernel {
     const Tensor& w = ctx->input(1);
     ConvGeom g;
     OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g));
-    float min_x = ctx->input(2).flat<float>()[0];
-    float max_x = ctx->input(3).flat<float>()[0];
-    float min_w = ctx->input(4).flat<float>()[0];
-    float max_w = ctx->input(5).flat<float>()[0];
+    float min_x = RangeIn(ctx, 2);
+    float max_x = RangeIn(ctx, 3);
+    float min_w = RangeIn(ctx, 4);
+    float max_w = RangeIn(ctx, 5);
     Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.K}));
     const uint8_t* xp = x.flat<uint8_t>();
     const uint8_t* wp = w.flat<uint8_t>();
@@ -166,10 +175,7 @@ class QuantizedConv2DOp : public OpKernel {
           int32_t* o = op + ((n * g.P + p) * g.Q + q) * g.K;
           for (int64_t k = 0; k < g.K; ++k) o[k] = (int32_t)acc[k];
         }
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
-        QuantProductMin(sx, sf);
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
-        QuantProductMax(sx, sf);
+    RangeOut(ctx, 1, QuantProductMin(sx, sf), QuantProductMax(sx, sf));
   }
 
  private:
@@ -183,8 +189,8 @@ class QuantizedReluOp : public OpKernel {
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    float mn = ctx->input(1).flat<float>()[0];
-    float mx = ctx->input(2).flat<float>()[0];
+    float mn = RangeIn(ctx, 1);
+    float mx = RangeIn(ctx, 2);
     Tensor* out = ctx->allocate_output(0, in.shape());
     // the quantized value representing 0.0
     int32_t zero_q = QuantZeroPoint(mn, mx);
@@ -192,8 +198,7 @@ class QuantizedReluOp : public OpKernel {
     uint8_t* o = out->flat<uint8_t>();
     for (int64_t i = 0; i < in.NumElements(); ++i)
       o[i] = (uint8_t)std::max<int32_t>(p[i], std::max(0, zero_q));
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = mn;
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = mx;
+    RangeOut(ctx, 1, mn, mx);
   }
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedRelu").Device(DEVICE_CPU),
@@ -204,19 +209,16 @@ class RequantizationRangeOp : public OpKernel {
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    float mn = ctx->input(1).flat<float>()[0];
-    float mx = ctx->input(2).flat<float>()[0];
-    double unit = ((double)mx - mn) / 4294967295.0;
+    float mn = RangeIn(ctx, 1);
+    float mx = RangeIn(ctx, 2);
+    double unit = QuantUnitI32(mn, mx);
     const int32_t* p = in.flat<int32_t>();
     int32_t lo = 0, hi = 0;
     for (int64_t i = 0; i < in.NumElements(); ++i) {
       lo = std::min(lo, p[i]);
       hi = std::max(hi, p[i]);
     }
-    ctx->allocate_output(0, TensorShape({}))->flat<float>()[0] =
-        (float)(lo * unit);
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
-        (float)(hi * unit);
+    RangeOut(ctx, 0, (float)(lo * unit), (float)(hi * unit));
   }
 };
 REGISTER_KERNEL_BUILDER(Name("RequantizationRange").Device(DEVICE_CPU),
@@ -227,9 +229,9 @@ class QuantizeDownAndShrinkRangeOp : public OpKernel {
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    float mn = ctx->input(1).flat<float>()[0];
-    float mx = ctx->input(2).flat<float>()[0];
-    double unit = ((double)mx - mn) / 4294967295.0;
+    float mn = RangeIn(ctx, 1);
+    float mx = RangeIn(ctx, 2);
+    double unit = QuantUnitI32(mn, mx);
     const int32_t* p = in.flat<int32_t>();
     int64_t n = in.NumElements();
     double lo = 0, hi = 0;
@@ -242,12 +244,9 @@ class QuantizeDownAndShrinkRangeOp : public OpKernel {
     Tensor* out = ctx->allocate_output(0, in.shape());
     uint8_t* o = out->flat<uint8_t>();
     double scale = 255.0 / (hi - lo);
-    for (int64_t i = 0; i < n; ++i) {
-      double v = (p[i] * unit - lo) * scale;
-      o[i] = (uint8_t)std::min(255.0, std::max(0.0, std::round(v)));
-    }
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = (float)lo;
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = (float)hi;
+    for (int64_t i = 0; i < n; ++i)
+      o[i] = QuantizeDownI32(p[i], unit, lo, scale);
+    RangeOut(ctx, 1, (float)lo, (float)hi);
   }
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizeDownAndShrinkRange").Device(DEVICE_CPU),
@@ -260,23 +259,20 @@ class RequantizeOp : public OpKernel {
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    float mn = ctx->input(1).flat<float>()[0];
-    float mx = ctx->input(2).flat<float>()[0];
-    double unit = ((double)mx - mn) / 4294967295.0;
-    double lo = (double)ctx->input(3).flat<float>()[0];
-    double hi = (double)ctx->input(4).flat<float>()[0];
+    float mn = RangeIn(ctx, 1);
+    float mx = RangeIn(ctx, 2);
+    double unit = QuantUnitI32(mn, mx);
+    double lo = (double)RangeIn(ctx, 3);
+    double hi = (double)RangeIn(ctx, 4);
     if (hi <= lo) hi = lo + 1e-6;
     const int32_t* p = in.flat<int32_t>();
     int64_t n = in.NumElements();
     Tensor* out = ctx->allocate_output(0, in.shape());
     uint8_t* o = out->flat<uint8_t>();
     double scale = 255.0 / (hi - lo);
-    for (int64_t i = 0; i < n; ++i) {
-      double v = (p[i] * unit - lo) * scale;
-      o[i] = (uint8_t)std::min(255.0, std::max(0.0, std::round(v)));
-    }
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = (float)lo;
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = (float)hi;
+    for (int64_t i = 0; i < n; ++i)
+      o[i] = QuantizeDownI32(p[i], unit, lo, scale);
+    RangeOut(ctx, 1, (float)lo, (float)hi);
   }
 };
 REGISTER_KERNEL_BUILDER(Name("Requantize").Device(DEVICE_CPU), RequantizeOp);
@@ -291,35 +287,17 @@ class QuantizedBiasAddOp : public OpKernel {
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
     const Tensor& bias = ctx->input(1);
-    OP_REQUIRES(ctx, in.dims() >= 1 && bias.dims() == 1 &&
-                         in.dim_size(in.dims() - 1) == bias.dim_size(0),
-                errors::InvalidArgument("QuantizedBiasAdd: the last input "
-                                        "dimension must equal the bias "
-                                        "length"));
-    float min_x = ctx->input(2).flat<float>()[0];
-    float max_x = ctx->input(3).flat<float>()[0];
-    float min_b = ctx->input(4).flat<float>()[0];
-    float max_b = ctx->input(5).flat<float>()[0];
-    float max_out = QuantBiasAddMax(min_x, max_x, min_b, max_b);
-    float min_out = -max_out;
-    double unit = ((double)max_out - min_out) / 4294967295.0;
-    float sx = QuantStep(min_x, max_x);
-    float sb = QuantStep(min_b, max_b);
-    int64_t C = bias.dim_size(0);
-    int64_t n = in.NumElements();
+    int64_t rows, C;
+    OP_REQUIRES_OK(ctx, QuantBiasAddDims(in.shape(), bias.shape(), &rows, &C));
+    QuantBiasAddScale sc = MakeQuantBiasAddScale(
+        RangeIn(ctx, 2), RangeIn(ctx, 3), RangeIn(ctx, 4), RangeIn(ctx, 5));
     Tensor* out = ctx->allocate_output(0, in.shape());
     const uint8_t* x = in.flat<uint8_t>();
     const uint8_t* b = bias.flat<uint8_t>();
     int32_t* o = out->flat<int32_t>();
-    for (int64_t i = 0; i < n; ++i) {
-      float fx = min_x + (float)x[i] * sx;
-      float fb = min_b + (float)b[i % C] * sb;
-      o[i] = unit == 0
-                 ? 0
-                 : (int32_t)std::round(((double)fx + (double)fb) / unit);
-    }
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = min_out;
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = max_out;
+    for (int64_t i = 0; i < rows * C; ++i)
+      o[i] = QuantBiasAddI32(x[i], b[i % C], sc);
+    RangeOut(ctx, 1, -sc.max_out, sc.max_out);
   }
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedBiasAdd").Device(DEVICE_CPU),
@@ -333,10 +311,7 @@ class QuantizedPoolOp : public OpKernel {
 
  protected:
   void ForwardRanges(OpKernelContext* ctx) const {
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] =
-        ctx->input(1).flat<float>()[0];
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] =
-        ctx->input(2).flat<float>()[0];
+    RangeOut(ctx, 1, RangeIn(ctx, 1), RangeIn(ctx, 2));
   }
   PoolAttrs attrs_;
 };
@@ -427,8 +402,8 @@ class QuantizedRelu6Op : public OpKernel {
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
-    float mn = ctx->input(1).flat<float>()[0];
-    float mx = ctx->input(2).flat<float>()[0];
+    float mn = RangeIn(ctx, 1);
+    float mx = RangeIn(ctx, 2);
     Tensor* out = ctx->allocate_output(0, in.shape());
     int32_t lo = QuantRelu6Floor(mn, mx);
     int32_t hi = QuantRelu6Ceil(mn, mx);
@@ -436,8 +411,7 @@ class QuantizedRelu6Op : public OpKernel {
     uint8_t* o = out->flat<uint8_t>();
     for (int64_t i = 0; i < in.NumElements(); ++i)
       o[i] = (uint8_t)std::min(std::max<int32_t>(p[i], lo), hi);
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = mn;
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = mx;
+    RangeOut(ctx, 1, mn, mx);
   }
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedRelu6").Device(DEVICE_CPU),
@@ -453,63 +427,30 @@ class QuantizedConcatOp : public OpKernel {
  public:
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
-    int n = (num_inputs() - 1) / 3;
-    const Tensor& first = ctx->input(1);
-    int rank = first.dims();
-    int64_t axis = IntVector(ctx->input(0))[0];
-    OP_REQUIRES(ctx, axis >= -rank && axis < rank,
-                errors::InvalidArgument("QuantizedConcat: concat_dim ", axis,
-                                        " out of range for rank ", rank));
-    if (axis < 0) axis += rank;
-    int64_t axis_total = 0;
-    for (int k = 0; k < n; ++k) {
-      const Tensor& t = ctx->input(1 + k);
-      OP_REQUIRES(ctx, t.dims() == rank,
-                  errors::InvalidArgument("QuantizedConcat: input ", k,
-                                          " has rank ", t.dims(),
-                                          ", input 0 has rank ", rank));
-      for (int d = 0; d < rank; ++d)
-        OP_REQUIRES(ctx, d == axis || t.dim_size(d) == first.dim_size(d),
-                    errors::InvalidArgument(
-                        "QuantizedConcat: input ", k, " has shape ",
-                        t.shape().DebugString(), ", input 0 has shape ",
-                        first.shape().DebugString(),
-                        "; they may differ on the concat axis only"));
-      axis_total += t.dim_size((int)axis);
-    }
-    TensorShape out_shape = first.shape();
-    out_shape.set_dim((int)axis, axis_total);
-    Tensor* out = ctx->allocate_output(0, out_shape);
-    int64_t outer = 1, inner = 1;
-    for (int i = 0; i < axis; ++i) outer *= first.dim_size(i);
-    for (int i = (int)axis + 1; i < rank; ++i) inner *= first.dim_size(i);
+    QuantConcatPlan plan;
+    OP_REQUIRES_OK(ctx, MakeQuantConcatPlan(ctx, num_inputs(), &plan));
+    Tensor* out = ctx->allocate_output(0, plan.out_shape);
     float lo = 0, hi = 0;
-    for (int k = 0; k < n; ++k)
-      QuantConcatRangeFold(ctx->input(1 + n + k).flat<float>()[0],
-                           ctx->input(1 + 2 * n + k).flat<float>()[0],
-                           k == 0, &lo, &hi);
+    for (int k = 0; k < plan.n; ++k)
+      QuantConcatRangeFold(RangeIn(ctx, plan.min(k)),
+                           RangeIn(ctx, plan.max(k)), k == 0, &lo, &hi);
     uint8_t* dst = out->flat<uint8_t>();
-    int64_t out_row = axis_total * inner;
-    int64_t off = 0;
-    for (int k = 0; k < n; ++k) {
-      const Tensor& t = ctx->input(1 + k);
-      float mn = ctx->input(1 + n + k).flat<float>()[0];
-      float mx = ctx->input(1 + 2 * n + k).flat<float>()[0];
-      int64_t row = t.dim_size((int)axis) * inner;
-      const uint8_t* src = t.flat<uint8_t>();
+    for (int k = 0; k < plan.n; ++k) {
+      float mn = RangeIn(ctx, plan.min(k));
+      float mx = RangeIn(ctx, plan.max(k));
+      int64_t row = plan.row[k];
+      const uint8_t* src = ctx->input(plan.value(k)).flat<uint8_t>();
       uint8_t lut[256];
       bool copy = mn == lo && mx == hi;
       for (int v = 0; v < 256; ++v)
         lut[v] = copy ? (uint8_t)v : RequantizeU8(v, mn, mx, lo, hi);
-      for (int64_t o = 0; o < outer; ++o) {
+      for (int64_t o = 0; o < plan.outer; ++o) {
         const uint8_t* s = src + o * row;
-        uint8_t* d = dst + o * out_row + off;
+        uint8_t* d = dst + o * plan.out_row + plan.off[k];
         for (int64_t j = 0; j < row; ++j) d[j] = lut[s[j]];
       }
-      off += row;
     }
-    ctx->allocate_output(1, TensorShape({}))->flat<float>()[0] = lo;
-    ctx->allocate_output(2, TensorShape({}))->flat<float>()[0] = hi;
+    RangeOut(ctx, 1, lo, hi);
   }
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedConcat").Device(DEVICE_CPU),

@@ -6,11 +6,12 @@
 //
 // The min/max ranges live in device memory on both sides of every op: only
 // QuantizedConcat's axis is in host memory and nothing here reads a range
-// value. The
-// kernels derive zero points and steps from the device scalars and write
-// the output ranges themselves, so a chain of quantized layers has no
-// device-to-host sync and replays inside a captured step.
+// value. The kernels derive zero points and steps from the device scalars
+// and write the output ranges themselves, so a chain of quantized layers has
+// no device-to-host sync and replays inside a captured step. The shape checks
+// shared with kernels/cpu_quantized.cc are in kernels/quantized_shapes.h.
 #include "kernels/gpu_common.h"
+#include "kernels/quantized_shapes.h"
 
 namespace stf {
 namespace {
@@ -84,13 +85,9 @@ class GpuQuantizedMatMulOp : public OpKernel {
     const Tensor& a = ctx->input(0);
     const Tensor& b = ctx->input(1);
     hipStream_t s = GPU_STREAM(ctx);
-    OP_REQUIRES(ctx, a.dims() == 2 && b.dims() == 2,
-                errors::InvalidArgument("QuantizedMatMul needs matrices"));
-    int64_t M = ta_ ? a.dim_size(1) : a.dim_size(0);
-    int64_t K = ta_ ? a.dim_size(0) : a.dim_size(1);
-    int64_t N = tb_ ? b.dim_size(0) : b.dim_size(1);
-    OP_REQUIRES(ctx, K == (tb_ ? b.dim_size(1) : b.dim_size(0)),
-                errors::InvalidArgument("QuantizedMatMul inner dim mismatch"));
+    int64_t M, N, K;
+    OP_REQUIRES_OK(ctx,
+                   QuantMatMulDims(a.shape(), b.shape(), ta_, tb_, &M, &N, &K));
     Tensor* out = ctx->allocate_output(0, TensorShape({M, N}));
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
@@ -165,22 +162,42 @@ class GpuQuantizedConv2DOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_GPU),
                         GpuQuantizedConv2DOp);
 
-class GpuQuantizedReluOp : public OpKernel {
+// QuantizedRelu and QuantizedRelu6: two entry points of one signature.
+using QuantizedClampFn = hipError_t (*)(const uint8_t*, const float*,
+                                       const float*, uint8_t*, float*,
+                                       float*, int64_t, hipStream_t);
+
+class GpuQuantizedClampOp : public OpKernel {
  public:
-  using OpKernel::OpKernel;
+  GpuQuantizedClampOp(OpKernelConstruction* c, QuantizedClampFn fn)
+      : OpKernel(c), fn_(fn) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
     Tensor* out = ctx->allocate_output(0, in.shape());
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
-    OP_HIP_OK(ctx, stf_quantized_relu((const uint8_t*)in.raw_data(),
-                                      F32(ctx->input(1)), F32(ctx->input(2)),
-                                      (uint8_t*)out->raw_data(), omn, omx,
-                                      in.NumElements(), GPU_STREAM(ctx)));
+    OP_HIP_OK(ctx, fn_((const uint8_t*)in.raw_data(), F32(ctx->input(1)),
+                       F32(ctx->input(2)), (uint8_t*)out->raw_data(), omn,
+                       omx, in.NumElements(), GPU_STREAM(ctx)));
   }
+
+ private:
+  QuantizedClampFn fn_;
+};
+class GpuQuantizedReluOp : public GpuQuantizedClampOp {
+ public:
+  explicit GpuQuantizedReluOp(OpKernelConstruction* c)
+      : GpuQuantizedClampOp(c, stf_quantized_relu) {}
+};
+class GpuQuantizedRelu6Op : public GpuQuantizedClampOp {
+ public:
+  explicit GpuQuantizedRelu6Op(OpKernelConstruction* c)
+      : GpuQuantizedClampOp(c, stf_quantized_relu6) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedRelu").Device(DEVICE_GPU),
                         GpuQuantizedReluOp);
+REGISTER_KERNEL_BUILDER(Name("QuantizedRelu6").Device(DEVICE_GPU),
+                        GpuQuantizedRelu6Op);
 
 class GpuRequantizationRangeOp : public OpKernel {
  public:
@@ -242,13 +259,8 @@ class GpuQuantizedBiasAddOp : public OpKernel {
   void Compute(OpKernelContext* ctx) override {
     const Tensor& in = ctx->input(0);
     const Tensor& bias = ctx->input(1);
-    OP_REQUIRES(ctx, in.dims() >= 1 && bias.dims() == 1 &&
-                         in.dim_size(in.dims() - 1) == bias.dim_size(0),
-                errors::InvalidArgument("QuantizedBiasAdd: the last input "
-                                        "dimension must equal the bias "
-                                        "length"));
-    int64_t C = bias.dim_size(0);
-    int64_t rows = C ? in.NumElements() / C : 0;
+    int64_t rows, C;
+    OP_REQUIRES_OK(ctx, QuantBiasAddDims(in.shape(), bias.shape(), &rows, &C));
     Tensor* out = ctx->allocate_output(0, in.shape());
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
@@ -305,23 +317,6 @@ REGISTER_KERNEL_BUILDER(Name("QuantizedMaxPool").Device(DEVICE_GPU),
 REGISTER_KERNEL_BUILDER(Name("QuantizedAvgPool").Device(DEVICE_GPU),
                         GpuQuantizedAvgPoolOp);
 
-class GpuQuantizedRelu6Op : public OpKernel {
- public:
-  using OpKernel::OpKernel;
-  void Compute(OpKernelContext* ctx) override {
-    const Tensor& in = ctx->input(0);
-    Tensor* out = ctx->allocate_output(0, in.shape());
-    float* omn = ScalarOut(ctx, 1);
-    float* omx = ScalarOut(ctx, 2);
-    OP_HIP_OK(ctx, stf_quantized_relu6((const uint8_t*)in.raw_data(),
-                                       F32(ctx->input(1)), F32(ctx->input(2)),
-                                       (uint8_t*)out->raw_data(), omn, omx,
-                                       in.NumElements(), GPU_STREAM(ctx)));
-  }
-};
-REGISTER_KERNEL_BUILDER(Name("QuantizedRelu6").Device(DEVICE_GPU),
-                        GpuQuantizedRelu6Op);
-
 // Only concat_dim is in host memory. The N range pairs stay on the device:
 // a range pass over all chunks of kStfQuantConcatMax inputs leaves the
 // output range in the two output scalars, then one copy launch per chunk
@@ -330,63 +325,33 @@ class GpuQuantizedConcatOp : public OpKernel {
  public:
   using OpKernel::OpKernel;
   void Compute(OpKernelContext* ctx) override {
-    int n = (num_inputs() - 1) / 3;
-    const Tensor& first = ctx->input(1);
-    int rank = first.dims();
-    int64_t axis = IntVector(ctx->input(0))[0];
-    OP_REQUIRES(ctx, axis >= -rank && axis < rank,
-                errors::InvalidArgument("QuantizedConcat: concat_dim ", axis,
-                                        " out of range for rank ", rank));
-    if (axis < 0) axis += rank;
-    int64_t axis_total = 0;
-    for (int k = 0; k < n; ++k) {
-      const Tensor& t = ctx->input(1 + k);
-      OP_REQUIRES(ctx, t.dims() == rank,
-                  errors::InvalidArgument("QuantizedConcat: input ", k,
-                                          " has rank ", t.dims(),
-                                          ", input 0 has rank ", rank));
-      for (int d = 0; d < rank; ++d)
-        OP_REQUIRES(ctx, d == axis || t.dim_size(d) == first.dim_size(d),
-                    errors::InvalidArgument(
-                        "QuantizedConcat: input ", k, " has shape ",
-                        t.shape().DebugString(), ", input 0 has shape ",
-                        first.shape().DebugString(),
-                        "; they may differ on the concat axis only"));
-      axis_total += t.dim_size((int)axis);
-    }
-    TensorShape out_shape = first.shape();
-    out_shape.set_dim((int)axis, axis_total);
-    Tensor* y = ctx->allocate_output(0, out_shape);
+    QuantConcatPlan plan;
+    OP_REQUIRES_OK(ctx, MakeQuantConcatPlan(ctx, num_inputs(), &plan));
+    Tensor* y = ctx->allocate_output(0, plan.out_shape);
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
-    int64_t outer = 1, inner = 1;
-    for (int i = 0; i < axis; ++i) outer *= first.dim_size(i);
-    for (int i = (int)axis + 1; i < rank; ++i) inner *= first.dim_size(i);
     hipStream_t s = GPU_STREAM(ctx);
     std::vector<StfQuantConcatArgs> chunks;
-    int64_t off = 0;
-    for (int k = 0; k < n; ++k) {
+    for (int k = 0; k < plan.n; ++k) {
       if (k % kStfQuantConcatMax == 0) {
         chunks.emplace_back();
         chunks.back().n = 0;
       }
       StfQuantConcatArgs& a = chunks.back();
-      const Tensor& t = ctx->input(1 + k);
       int j = a.n++;
-      a.src[j] = (const uint8_t*)t.raw_data();
-      a.mn[j] = F32(ctx->input(1 + n + k));
-      a.mx[j] = F32(ctx->input(1 + 2 * n + k));
-      a.inner[j] = t.dim_size((int)axis) * inner;
-      a.off[j] = off;
-      off += a.inner[j];
+      a.src[j] = (const uint8_t*)ctx->input(plan.value(k)).raw_data();
+      a.mn[j] = F32(ctx->input(plan.min(k)));
+      a.mx[j] = F32(ctx->input(plan.max(k)));
+      a.inner[j] = plan.row[k];
+      a.off[j] = plan.off[k];
     }
     for (size_t c = 0; c < chunks.size(); ++c)
       OP_HIP_OK(ctx, stf_quantized_concat_range(&chunks[c], c == 0, omn, omx,
                                                 s));
     for (size_t c = 0; c < chunks.size(); ++c)
       OP_HIP_OK(ctx, stf_quantized_concat_copy(&chunks[c], omn, omx,
-                                               (uint8_t*)y->raw_data(), outer,
-                                               off, s));
+                                               (uint8_t*)y->raw_data(),
+                                               plan.outer, plan.out_row, s));
   }
 };
 REGISTER_KERNEL_BUILDER(

@@ -3,12 +3,13 @@
 // Requantize, QuantizedBiasAdd, QuantizedMaxPool, QuantizedAvgPool,
 // QuantizedRelu6, QuantizedConcat.
 //
-// Every output is bit-equal to kernels/cpu_quantized.cc: the same IEEE
-// operations in the same order and precision (f32 for the quint8 paths, f64
-// for the qint32 paths), with floating-point contraction off so that
-// mn + q * step is never fused into an FMA. The ranges are device scalars,
-// read through pointers and written by the kernels, so a chain of quantized
-// layers never synchronises with the host.
+// Every output is bit-equal to kernels/cpu_quantized.cc. The per-element
+// formulas are not written here: both sides call the one definition in
+// kernels/quantized_util.h, which keeps its own multiplies and adds from
+// contracting; contraction is off in this file as well, for the range
+// arithmetic that stays here. The ranges are device scalars, read through
+// pointers and written by the kernels, so a chain of quantized layers never
+// synchronises with the host.
 #include "hip_common.h"
 #include "kernels/quantized_util.h"
 #include "stf_kernels.h"
@@ -17,12 +18,28 @@
 
 namespace {
 
-__device__ __forceinline__ uint8_t QuantizeOne(float x, float mn,
-                                               float scale) {
-  float q = roundf((x - mn) * scale);
-  float lo = 0.f < q ? q : 0.f;          // std::max(0.f, q)
-  float v = lo < 255.f ? lo : 255.f;     // std::min(255.f, .)
-  return (uint8_t)v;
+// The calling thread's first index and step in a grid-stride loop.
+struct GridThread {
+  int64_t tid, stride;
+};
+
+// The block size comes from the builtin: blockDim.x, read outside a
+// __global__ function, compiles to the lookup that allows for a partial last
+// block, which costs every kernel a global load in its prologue.
+__device__ __forceinline__ GridThread ThisThread() {
+  uint32_t block = __builtin_amdgcn_workgroup_size_x();
+  return {(int64_t)blockIdx.x * block + threadIdx.x,
+          (int64_t)gridDim.x * block};
+}
+
+// Thread 0 of the grid writes the op's two output range scalars.
+__device__ __forceinline__ void WriteRanges(const GridThread& t,
+                                            float* out_mn, float* out_mx,
+                                            float mn, float mx) {
+  if (t.tid == 0) {
+    out_mn[0] = mn;
+    out_mx[0] = mx;
+  }
 }
 
 __global__ void QuantizeV2Kernel(const float* __restrict__ x,
@@ -34,23 +51,19 @@ __global__ void QuantizeV2Kernel(const float* __restrict__ x,
   float mn = mnp[0], mx = mxp[0];
   if (mx <= mn) mx = mn + 1e-6f;
   float scale = 255.f / (mx - mn);
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = mn;
-    out_mx[0] = mx;
-  }
+  GridThread t = ThisThread();
+  WriteRanges(t, out_mn, out_mx, mn, mx);
   int64_t n4 = n / 4;
-  for (int64_t i = tid; i < n4; i += stride) {
+  for (int64_t i = t.tid; i < n4; i += t.stride) {
     float4 v = ((const float4*)x)[i];
-    uint32_t w = (uint32_t)QuantizeOne(v.x, mn, scale) |
-                 (uint32_t)QuantizeOne(v.y, mn, scale) << 8 |
-                 (uint32_t)QuantizeOne(v.z, mn, scale) << 16 |
-                 (uint32_t)QuantizeOne(v.w, mn, scale) << 24;
+    uint32_t w = (uint32_t)stf::QuantizeU8(v.x, mn, scale) |
+                 (uint32_t)stf::QuantizeU8(v.y, mn, scale) << 8 |
+                 (uint32_t)stf::QuantizeU8(v.z, mn, scale) << 16 |
+                 (uint32_t)stf::QuantizeU8(v.w, mn, scale) << 24;
     ((uint32_t*)y)[i] = w;
   }
-  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
-    y[i] = QuantizeOne(x[i], mn, scale);
+  for (int64_t i = n4 * 4 + t.tid; i < n; i += t.stride)
+    y[i] = stf::QuantizeU8(x[i], mn, scale);
 }
 
 __global__ void DequantizeU8Kernel(const uint8_t* __restrict__ x,
@@ -59,25 +72,19 @@ __global__ void DequantizeU8Kernel(const uint8_t* __restrict__ x,
                                    float* __restrict__ y, int64_t n) {
   float mn = mnp[0];
   float step = stf::QuantStep(mn, mxp[0]);
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  GridThread t = ThisThread();
   int64_t n4 = n / 4;
-  for (int64_t i = tid; i < n4; i += stride) {
+  for (int64_t i = t.tid; i < n4; i += t.stride) {
     uint32_t w = ((const uint32_t*)x)[i];
     float4 o;
-    o.x = mn + (float)(w & 0xff) * step;
-    o.y = mn + (float)((w >> 8) & 0xff) * step;
-    o.z = mn + (float)((w >> 16) & 0xff) * step;
-    o.w = mn + (float)(w >> 24) * step;
+    o.x = stf::DequantizeU8(w & 0xff, mn, step);
+    o.y = stf::DequantizeU8((w >> 8) & 0xff, mn, step);
+    o.z = stf::DequantizeU8((w >> 16) & 0xff, mn, step);
+    o.w = stf::DequantizeU8(w >> 24, mn, step);
     ((float4*)y)[i] = o;
   }
-  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
-    y[i] = mn + (float)x[i] * step;
-}
-
-__device__ __forceinline__ float DequantizeI32One(int32_t p, double scale,
-                                                  float mn) {
-  return (float)(((double)p + 2147483648.0) * scale + mn);
+  for (int64_t i = n4 * 4 + t.tid; i < n; i += t.stride)
+    y[i] = stf::DequantizeU8(x[i], mn, step);
 }
 
 __global__ void DequantizeI32Kernel(const int32_t* __restrict__ x,
@@ -85,21 +92,20 @@ __global__ void DequantizeI32Kernel(const int32_t* __restrict__ x,
                                     const float* __restrict__ mxp,
                                     float* __restrict__ y, int64_t n) {
   float mn = mnp[0];
-  double scale = ((double)mxp[0] - mn) / 4294967295.0;
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  double scale = stf::QuantUnitI32(mn, mxp[0]);
+  GridThread t = ThisThread();
   int64_t n4 = n / 4;
-  for (int64_t i = tid; i < n4; i += stride) {
+  for (int64_t i = t.tid; i < n4; i += t.stride) {
     int4 v = ((const int4*)x)[i];
     float4 o;
-    o.x = DequantizeI32One(v.x, scale, mn);
-    o.y = DequantizeI32One(v.y, scale, mn);
-    o.z = DequantizeI32One(v.z, scale, mn);
-    o.w = DequantizeI32One(v.w, scale, mn);
+    o.x = stf::DequantizeI32(v.x, scale, mn);
+    o.y = stf::DequantizeI32(v.y, scale, mn);
+    o.z = stf::DequantizeI32(v.z, scale, mn);
+    o.w = stf::DequantizeI32(v.w, scale, mn);
     ((float4*)y)[i] = o;
   }
-  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
-    y[i] = DequantizeI32One(x[i], scale, mn);
+  for (int64_t i = n4 * 4 + t.tid; i < n; i += t.stride)
+    y[i] = stf::DequantizeI32(x[i], scale, mn);
 }
 
 // max per byte of the four u8 lanes of a word against one floor value
@@ -122,14 +128,10 @@ __global__ void QuantizedReluKernel(const uint8_t* __restrict__ x,
   float mn = mnp[0], mx = mxp[0];
   int32_t zero_q = stf::QuantZeroPoint(mn, mx);
   int32_t floor_q = zero_q > 0 ? zero_q : 0;
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = mn;
-    out_mx[0] = mx;
-  }
+  GridThread t = ThisThread();
+  WriteRanges(t, out_mn, out_mx, mn, mx);
   int64_t n16 = n / 16;
-  for (int64_t i = tid; i < n16; i += stride) {
+  for (int64_t i = t.tid; i < n16; i += t.stride) {
     uint4 v = ((const uint4*)x)[i];
     v.x = MaxU8x4(v.x, floor_q);
     v.y = MaxU8x4(v.y, floor_q);
@@ -137,7 +139,7 @@ __global__ void QuantizedReluKernel(const uint8_t* __restrict__ x,
     v.w = MaxU8x4(v.w, floor_q);
     ((uint4*)y)[i] = v;
   }
-  for (int64_t i = n16 * 16 + tid; i < n; i += stride) {
+  for (int64_t i = n16 * 16 + t.tid; i < n; i += t.stride) {
     int32_t p = x[i];
     y[i] = (uint8_t)(p > floor_q ? p : floor_q);
   }
@@ -148,16 +150,15 @@ __global__ void QuantizedReluKernel(const uint8_t* __restrict__ x,
 __global__ void MinMaxI32Kernel(const int32_t* __restrict__ x,
                                 int32_t* __restrict__ lohi, int64_t n) {
   __shared__ int32_t slo[4], shi[4];
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  GridThread t = ThisThread();
   int32_t lo = 0, hi = 0;
   int64_t n4 = n / 4;
-  for (int64_t i = tid; i < n4; i += stride) {
+  for (int64_t i = t.tid; i < n4; i += t.stride) {
     int4 v = ((const int4*)x)[i];
     lo = min(lo, min(min(v.x, v.y), min(v.z, v.w)));
     hi = max(hi, max(max(v.x, v.y), max(v.z, v.w)));
   }
-  for (int64_t i = n4 * 4 + tid; i < n; i += stride) {
+  for (int64_t i = n4 * 4 + t.tid; i < n; i += t.stride) {
     lo = min(lo, x[i]);
     hi = max(hi, x[i]);
   }
@@ -186,7 +187,7 @@ __global__ void RequantRangeKernel(const int32_t* __restrict__ lohi,
                                    float* __restrict__ out_mn,
                                    float* __restrict__ out_mx) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double unit = ((double)mxp[0] - mnp[0]) / 4294967295.0;
+  double unit = stf::QuantUnitI32(mnp[0], mxp[0]);
   out_mn[0] = (float)(lohi[0] * unit);
   out_mx[0] = (float)(lohi[1] * unit);
 }
@@ -207,12 +208,13 @@ __device__ __forceinline__ void ShrunkRange(const int32_t* lohi, double unit,
   *hi = h;
 }
 
-__device__ __forceinline__ uint8_t QuantizeDownOne(int32_t p, double unit,
-                                                   double lo, double scale) {
-  double v = round((p * unit - lo) * scale);
-  double m = 0.0 < v ? v : 0.0;
-  m = m < 255.0 ? m : 255.0;
-  return (uint8_t)m;
+__device__ __forceinline__ uint32_t QuantizeDownFour(int4 v, double unit,
+                                                     double lo,
+                                                     double scale) {
+  return (uint32_t)stf::QuantizeDownI32(v.x, unit, lo, scale) |
+         (uint32_t)stf::QuantizeDownI32(v.y, unit, lo, scale) << 8 |
+         (uint32_t)stf::QuantizeDownI32(v.z, unit, lo, scale) << 16 |
+         (uint32_t)stf::QuantizeDownI32(v.w, unit, lo, scale) << 24;
 }
 
 __global__ void QuantizeDownKernel(const int32_t* __restrict__ x,
@@ -222,36 +224,18 @@ __global__ void QuantizeDownKernel(const int32_t* __restrict__ x,
                                    uint8_t* __restrict__ y,
                                    float* __restrict__ out_mn,
                                    float* __restrict__ out_mx, int64_t n) {
-  double unit = ((double)mxp[0] - mnp[0]) / 4294967295.0;
+  double unit = stf::QuantUnitI32(mnp[0], mxp[0]);
   double lo, hi;
   ShrunkRange(lohi, unit, &lo, &hi);
   double scale = 255.0 / (hi - lo);
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = (float)lo;
-    out_mx[0] = (float)hi;
-  }
+  GridThread t = ThisThread();
+  WriteRanges(t, out_mn, out_mx, (float)lo, (float)hi);
   int64_t n4 = n / 4;
-  for (int64_t i = tid; i < n4; i += stride) {
-    int4 v = ((const int4*)x)[i];
-    uint32_t w = (uint32_t)QuantizeDownOne(v.x, unit, lo, scale) |
-                 (uint32_t)QuantizeDownOne(v.y, unit, lo, scale) << 8 |
-                 (uint32_t)QuantizeDownOne(v.z, unit, lo, scale) << 16 |
-                 (uint32_t)QuantizeDownOne(v.w, unit, lo, scale) << 24;
-    ((uint32_t*)y)[i] = w;
-  }
-  for (int64_t i = n4 * 4 + tid; i < n; i += stride)
-    y[i] = QuantizeDownOne(x[i], unit, lo, scale);
-}
-
-__device__ __forceinline__ uint32_t QuantizeDownFour(int4 v, double unit,
-                                                     double lo,
-                                                     double scale) {
-  return (uint32_t)QuantizeDownOne(v.x, unit, lo, scale) |
-         (uint32_t)QuantizeDownOne(v.y, unit, lo, scale) << 8 |
-         (uint32_t)QuantizeDownOne(v.z, unit, lo, scale) << 16 |
-         (uint32_t)QuantizeDownOne(v.w, unit, lo, scale) << 24;
+  for (int64_t i = t.tid; i < n4; i += t.stride)
+    ((uint32_t*)y)[i] =
+        QuantizeDownFour(((const int4*)x)[i], unit, lo, scale);
+  for (int64_t i = n4 * 4 + t.tid; i < n; i += t.stride)
+    y[i] = stf::QuantizeDownI32(x[i], unit, lo, scale);
 }
 
 // QuantizeDownKernel with the range given: no reduction in front of it. A
@@ -265,18 +249,14 @@ __global__ void RequantizeKernel(const int32_t* __restrict__ x,
                                  uint8_t* __restrict__ y,
                                  float* __restrict__ out_mn,
                                  float* __restrict__ out_mx, int64_t n) {
-  double unit = ((double)mxp[0] - mnp[0]) / 4294967295.0;
+  double unit = stf::QuantUnitI32(mnp[0], mxp[0]);
   double lo = (double)req_mn[0], hi = (double)req_mx[0];
   if (hi <= lo) hi = lo + 1e-6;
   double scale = 255.0 / (hi - lo);
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = (float)lo;
-    out_mx[0] = (float)hi;
-  }
+  GridThread t = ThisThread();
+  WriteRanges(t, out_mn, out_mx, (float)lo, (float)hi);
   int64_t n16 = n / 16;
-  for (int64_t i = tid; i < n16; i += stride) {
+  for (int64_t i = t.tid; i < n16; i += t.stride) {
     const int4* src = (const int4*)x + i * 4;
     int4 a = src[0], b = src[1], c = src[2], d = src[3];
     uint4 o;
@@ -286,38 +266,8 @@ __global__ void RequantizeKernel(const int32_t* __restrict__ x,
     o.w = QuantizeDownFour(d, unit, lo, scale);
     ((uint4*)y)[i] = o;
   }
-  for (int64_t i = n16 * 16 + tid; i < n; i += stride)
-    y[i] = QuantizeDownOne(x[i], unit, lo, scale);
-}
-
-// The range of a QuantizedBiasAdd result and the qint32 unit of that range.
-struct BiasAddScale {
-  float min_x, step_x, min_b, step_b, max_out;
-  double unit;
-};
-
-__device__ __forceinline__ BiasAddScale MakeBiasAddScale(
-    const float* min_x, const float* max_x, const float* min_b,
-    const float* max_b) {
-  BiasAddScale s;
-  s.min_x = min_x[0];
-  s.min_b = min_b[0];
-  s.step_x = stf::QuantStep(s.min_x, max_x[0]);
-  s.step_b = stf::QuantStep(s.min_b, max_b[0]);
-  s.max_out = stf::QuantBiasAddMax(s.min_x, max_x[0], s.min_b, max_b[0]);
-  float min_out = -s.max_out;
-  s.unit = ((double)s.max_out - min_out) / 4294967295.0;
-  return s;
-}
-
-// The f64 divide is the CPU kernel's: a reciprocal multiply rounds
-// differently.
-__device__ __forceinline__ int32_t BiasAddOne(uint32_t x, uint32_t b,
-                                              const BiasAddScale& s) {
-  float fx = s.min_x + (float)x * s.step_x;
-  float fb = s.min_b + (float)b * s.step_b;
-  if (s.unit == 0) return 0;
-  return (int32_t)round(((double)fx + (double)fb) / s.unit);
+  for (int64_t i = n16 * 16 + t.tid; i < n; i += t.stride)
+    y[i] = stf::QuantizeDownI32(x[i], unit, lo, scale);
 }
 
 // x viewed as [rows, C]. VEC: C % 4 == 0 and a thread takes 4 consecutive
@@ -333,28 +283,25 @@ __global__ void QuantizedBiasAddKernel(const uint8_t* __restrict__ x,
                                        float* __restrict__ out_mn,
                                        float* __restrict__ out_mx,
                                        int64_t total, int64_t C) {
-  BiasAddScale s = MakeBiasAddScale(min_x, max_x, min_b, max_b);
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = -s.max_out;
-    out_mx[0] = s.max_out;
-  }
+  stf::QuantBiasAddScale s =
+      stf::MakeQuantBiasAddScale(min_x[0], max_x[0], min_b[0], max_b[0]);
+  GridThread t = ThisThread();
+  WriteRanges(t, out_mn, out_mx, -s.max_out, s.max_out);
   if (VEC) {
     int64_t c4 = C / 4;
-    for (int64_t i = tid; i < total; i += stride) {
+    for (int64_t i = t.tid; i < total; i += t.stride) {
       uint32_t xv = ((const uint32_t*)x)[i];
       uint32_t bv = ((const uint32_t*)bias)[i % c4];
       int4 o;
-      o.x = BiasAddOne(xv & 0xff, bv & 0xff, s);
-      o.y = BiasAddOne((xv >> 8) & 0xff, (bv >> 8) & 0xff, s);
-      o.z = BiasAddOne((xv >> 16) & 0xff, (bv >> 16) & 0xff, s);
-      o.w = BiasAddOne(xv >> 24, bv >> 24, s);
+      o.x = stf::QuantBiasAddI32(xv & 0xff, bv & 0xff, s);
+      o.y = stf::QuantBiasAddI32((xv >> 8) & 0xff, (bv >> 8) & 0xff, s);
+      o.z = stf::QuantBiasAddI32((xv >> 16) & 0xff, (bv >> 16) & 0xff, s);
+      o.w = stf::QuantBiasAddI32(xv >> 24, bv >> 24, s);
       ((int4*)y)[i] = o;
     }
   } else {
-    for (int64_t i = tid; i < total; i += stride)
-      y[i] = BiasAddOne(x[i], bias[i % C], s);
+    for (int64_t i = t.tid; i < total; i += t.stride)
+      y[i] = stf::QuantBiasAddI32(x[i], bias[i % C], s);
   }
 }
 
@@ -389,81 +336,6 @@ __device__ __forceinline__ void PoolWindow(const StfPoolGeom& g, int p, int q,
   *w1 = min(q * g.sw - g.pw + g.kw, g.W);
 }
 
-// C % 16 == 0: a thread owns 16 channels of one output pixel. The window is
-// clipped to the image, so every tap that is read lies inside it.
-__global__ void QuantizedMaxPoolV16Kernel(const uint8_t* __restrict__ x,
-                                          const float* __restrict__ mnp,
-                                          const float* __restrict__ mxp,
-                                          uint8_t* __restrict__ y,
-                                          float* __restrict__ out_mn,
-                                          float* __restrict__ out_mx,
-                                          StfPoolGeom g, int64_t total16) {
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = mnp[0];
-    out_mx[0] = mxp[0];
-  }
-  int64_t c16 = g.C / 16;
-  for (int64_t i = tid; i < total16; i += stride) {
-    int64_t rem = i;
-    int64_t cw = rem % c16; rem /= c16;
-    int q = (int)(rem % g.Q); rem /= g.Q;
-    int p = (int)(rem % g.P); rem /= g.P;
-    int64_t n = rem;
-    int h0, h1, w0, w1;
-    PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
-    MaxU8x4Acc a0, a1, a2, a3;
-    for (int ih = h0; ih < h1; ++ih)
-      for (int iw = w0; iw < w1; ++iw) {
-        uint4 v = *(const uint4*)(x + ((n * g.H + ih) * g.W + iw) * g.C +
-                                  cw * 16);
-        a0.Take(v.x);
-        a1.Take(v.y);
-        a2.Take(v.z);
-        a3.Take(v.w);
-      }
-    uint4 o;
-    o.x = a0.Word();
-    o.y = a1.Word();
-    o.z = a2.Word();
-    o.w = a3.Word();
-    // ((n * P + p) * Q + q) * C + cw * 16 == i * 16
-    ((uint4*)y)[i] = o;
-  }
-}
-
-__global__ void QuantizedMaxPoolKernel(const uint8_t* __restrict__ x,
-                                       const float* __restrict__ mnp,
-                                       const float* __restrict__ mxp,
-                                       uint8_t* __restrict__ y,
-                                       float* __restrict__ out_mn,
-                                       float* __restrict__ out_mx,
-                                       StfPoolGeom g, int64_t total) {
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = mnp[0];
-    out_mx[0] = mxp[0];
-  }
-  for (int64_t i = tid; i < total; i += stride) {
-    int64_t rem = i;
-    int64_t c = rem % g.C; rem /= g.C;
-    int q = (int)(rem % g.Q); rem /= g.Q;
-    int p = (int)(rem % g.P); rem /= g.P;
-    int64_t n = rem;
-    int h0, h1, w0, w1;
-    PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
-    uint32_t best = 0;
-    for (int ih = h0; ih < h1; ++ih)
-      for (int iw = w0; iw < w1; ++iw) {
-        uint32_t v = x[((n * g.H + ih) * g.W + iw) * g.C + c];
-        best = best < v ? v : best;
-      }
-    y[i] = (uint8_t)best;
-  }
-}
-
 // Sums of the four u8 lanes of a word, in 32 bits: 255 * taps overflows 16
 // bits once a window has more than 257 taps, and 32 bits hold any window.
 __device__ __forceinline__ void AddU8x4(uint32_t w, uint32_t* acc) {
@@ -495,90 +367,131 @@ __device__ __forceinline__ uint32_t PoolTaps(int h0, int h1, int w0, int w1) {
   return cnt > 0 ? (uint32_t)cnt : 1u;
 }
 
-// QuantizedMaxPoolV16Kernel's scheme with sixteen u32 sums per thread.
-__global__ void QuantizedAvgPoolV16Kernel(const uint8_t* __restrict__ x,
-                                          const float* __restrict__ mnp,
-                                          const float* __restrict__ mxp,
-                                          uint8_t* __restrict__ y,
-                                          float* __restrict__ out_mn,
-                                          float* __restrict__ out_mx,
-                                          StfPoolGeom g, int64_t total16) {
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = mnp[0];
-    out_mx[0] = mxp[0];
-  }
-  int64_t c16 = g.C / 16;
-  for (int64_t i = tid; i < total16; i += stride) {
-    int64_t rem = i;
-    int64_t cw = rem % c16; rem /= c16;
-    int q = (int)(rem % g.Q); rem /= g.Q;
-    int p = (int)(rem % g.P); rem /= g.P;
-    int64_t n = rem;
-    int h0, h1, w0, w1;
-    PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
-    uint32_t acc[16];
-#pragma unroll
-    for (int b = 0; b < 16; ++b) acc[b] = 0;
-    // Four taps of a row at a time, their loads issued before the first sum
-    // so that they are in flight together: a global-pool head (8x8 on 2048
-    // channels) has few threads with 64 taps each and is bound by the
-    // latency of a tap's load.
-    for (int ih = h0; ih < h1; ++ih) {
-      const uint8_t* row = x + ((n * g.H + ih) * g.W) * g.C + cw * 16;
-      int iw = w0;
-      for (; iw + 4 <= w1; iw += 4) {
-        const uint8_t* t = row + (int64_t)iw * g.C;
-        uint4 v0 = *(const uint4*)t;
-        uint4 v1 = *(const uint4*)(t + g.C);
-        uint4 v2 = *(const uint4*)(t + 2 * (int64_t)g.C);
-        uint4 v3 = *(const uint4*)(t + 3 * (int64_t)g.C);
-        AddU8x16(v0, acc);
-        AddU8x16(v1, acc);
-        AddU8x16(v2, acc);
-        AddU8x16(v3, acc);
-      }
-      for (; iw < w1; ++iw)
-        AddU8x16(*(const uint4*)(row + (int64_t)iw * g.C), acc);
-    }
-    uint32_t cnt = PoolTaps(h0, h1, w0, w1);
-    uint4 o;
-    o.x = DivU8x4(acc, cnt);
-    o.y = DivU8x4(acc + 4, cnt);
-    o.z = DivU8x4(acc + 8, cnt);
-    o.w = DivU8x4(acc + 12, cnt);
-    // ((n * P + p) * Q + q) * C + cw * 16 == i * 16
-    ((uint4*)y)[i] = o;
-  }
-}
+// The reducers of QuantizedPoolKernel, for G = 16 or 1 channels per thread.
+// State starts zeroed. Row() takes the taps w0..w1-1 of the image row whose
+// first pixel is pixel `pix` of x, at the thread's channel offset c; Store()
+// writes the G results of output group i, given the window's tap count. The
+// functions are static and the kernel holds the State as a plain local: as
+// members of a reducer object, PoolAvg<16>'s sums are split up differently by
+// the compiler, and the kernel needs 72 VGPRs or more where it has 63.
+template <int G>
+struct PoolMax;
 
-__global__ void QuantizedAvgPoolKernel(const uint8_t* __restrict__ x,
-                                       const float* __restrict__ mnp,
-                                       const float* __restrict__ mxp,
-                                       uint8_t* __restrict__ y,
-                                       float* __restrict__ out_mn,
-                                       float* __restrict__ out_mx,
-                                       StfPoolGeom g, int64_t total) {
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = mnp[0];
-    out_mx[0] = mxp[0];
+template <>
+struct PoolMax<16> {
+  using State = MaxU8x4Acc[4];
+  static __device__ __forceinline__ void Row(State& a, const uint8_t* x,
+                                             int64_t pix, int64_t c, int w0,
+                                             int w1, int C) {
+    for (int iw = w0; iw < w1; ++iw) {
+      uint4 v = *(const uint4*)(x + (pix + iw) * C + c);
+      a[0].Take(v.x);
+      a[1].Take(v.y);
+      a[2].Take(v.z);
+      a[3].Take(v.w);
+    }
   }
-  for (int64_t i = tid; i < total; i += stride) {
+  static __device__ __forceinline__ void Store(const State& a, uint8_t* y,
+                                               int64_t i, uint32_t) {
+    ((uint4*)y)[i] = uint4{a[0].Word(), a[1].Word(), a[2].Word(), a[3].Word()};
+  }
+};
+
+template <>
+struct PoolMax<1> {
+  using State = uint32_t;
+  static __device__ __forceinline__ void Row(State& best, const uint8_t* x,
+                                             int64_t pix, int64_t c, int w0,
+                                             int w1, int C) {
+    for (int iw = w0; iw < w1; ++iw) {
+      uint32_t v = x[(pix + iw) * C + c];
+      best = best < v ? v : best;
+    }
+  }
+  static __device__ __forceinline__ void Store(const State& best, uint8_t* y,
+                                               int64_t i, uint32_t) {
+    y[i] = (uint8_t)best;
+  }
+};
+
+template <int G>
+struct PoolAvg;
+
+template <>
+struct PoolAvg<16> {
+  using State = uint32_t[16];
+  // Four taps of a row at a time, their loads issued before the first sum so
+  // that they are in flight together: a global-pool head (8x8 on 2048
+  // channels) has few threads with 64 taps each and is bound by the latency
+  // of a tap's load.
+  static __device__ __forceinline__ void Row(State& acc, const uint8_t* x,
+                                             int64_t pix, int64_t c, int w0,
+                                             int w1, int C) {
+    const uint8_t* row = x + pix * C + c;
+    int iw = w0;
+    for (; iw + 4 <= w1; iw += 4) {
+      const uint8_t* t = row + (int64_t)iw * C;
+      uint4 v0 = *(const uint4*)t;
+      uint4 v1 = *(const uint4*)(t + C);
+      uint4 v2 = *(const uint4*)(t + 2 * (int64_t)C);
+      uint4 v3 = *(const uint4*)(t + 3 * (int64_t)C);
+      AddU8x16(v0, acc);
+      AddU8x16(v1, acc);
+      AddU8x16(v2, acc);
+      AddU8x16(v3, acc);
+    }
+    for (; iw < w1; ++iw)
+      AddU8x16(*(const uint4*)(row + (int64_t)iw * C), acc);
+  }
+  static __device__ __forceinline__ void Store(const State& acc, uint8_t* y,
+                                               int64_t i, uint32_t taps) {
+    ((uint4*)y)[i] = uint4{DivU8x4(acc, taps), DivU8x4(acc + 4, taps),
+                           DivU8x4(acc + 8, taps), DivU8x4(acc + 12, taps)};
+  }
+};
+
+template <>
+struct PoolAvg<1> {
+  using State = uint32_t;
+  static __device__ __forceinline__ void Row(State& sum, const uint8_t* x,
+                                             int64_t pix, int64_t c, int w0,
+                                             int w1, int C) {
+    for (int iw = w0; iw < w1; ++iw) sum += x[(pix + iw) * C + c];
+  }
+  static __device__ __forceinline__ void Store(const State& sum, uint8_t* y,
+                                               int64_t i, uint32_t taps) {
+    y[i] = (uint8_t)(sum / taps);
+  }
+};
+
+// The NHWC quint8 pools. A thread owns G channels of one output pixel: 16
+// when C % 16 == 0, else 1; `total` counts those groups. The window is
+// clipped to the image, so every tap that is read lies inside it. Both pools
+// pass their ranges through.
+template <template <int> class Reducer, int G>
+__global__ void QuantizedPoolKernel(const uint8_t* __restrict__ x,
+                                    const float* __restrict__ mnp,
+                                    const float* __restrict__ mxp,
+                                    uint8_t* __restrict__ y,
+                                    float* __restrict__ out_mn,
+                                    float* __restrict__ out_mx,
+                                    StfPoolGeom g, int64_t total) {
+  GridThread t = ThisThread();
+  WriteRanges(t, out_mn, out_mx, mnp[0], mxp[0]);
+  int64_t groups = g.C / G;
+  for (int64_t i = t.tid; i < total; i += t.stride) {
     int64_t rem = i;
-    int64_t c = rem % g.C; rem /= g.C;
+    int64_t c = rem % groups; rem /= groups;
     int q = (int)(rem % g.Q); rem /= g.Q;
     int p = (int)(rem % g.P); rem /= g.P;
     int64_t n = rem;
     int h0, h1, w0, w1;
     PoolWindow(g, p, q, &h0, &h1, &w0, &w1);
-    uint32_t sum = 0;
+    typename Reducer<G>::State r{};
     for (int ih = h0; ih < h1; ++ih)
-      for (int iw = w0; iw < w1; ++iw)
-        sum += x[((n * g.H + ih) * g.W + iw) * g.C + c];
-    y[i] = (uint8_t)(sum / PoolTaps(h0, h1, w0, w1));
+      Reducer<G>::Row(r, x, (n * g.H + ih) * g.W, c * G, w0, w1, g.C);
+    // ((n * P + p) * Q + q) * C + c * G == i * G
+    Reducer<G>::Store(r, y, i, PoolTaps(h0, h1, w0, w1));
   }
 }
 
@@ -612,14 +525,10 @@ __global__ void QuantizedRelu6Kernel(const uint8_t* __restrict__ x,
   int32_t hi = stf::QuantRelu6Ceil(mn, mx);
   uint32_t lo2 = (uint32_t)lo | (uint32_t)lo << 16;
   uint32_t hi2 = (uint32_t)hi | (uint32_t)hi << 16;
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (tid == 0) {
-    out_mn[0] = mn;
-    out_mx[0] = mx;
-  }
+  GridThread t = ThisThread();
+  WriteRanges(t, out_mn, out_mx, mn, mx);
   int64_t n16 = n / 16;
-  for (int64_t i = tid; i < n16; i += stride) {
+  for (int64_t i = t.tid; i < n16; i += t.stride) {
     uint4 v = ((const uint4*)x)[i];
     v.x = ClampU8x4(v.x, lo2, hi2);
     v.y = ClampU8x4(v.y, lo2, hi2);
@@ -627,7 +536,7 @@ __global__ void QuantizedRelu6Kernel(const uint8_t* __restrict__ x,
     v.w = ClampU8x4(v.w, lo2, hi2);
     ((uint4*)y)[i] = v;
   }
-  for (int64_t i = n16 * 16 + tid; i < n; i += stride) {
+  for (int64_t i = n16 * 16 + t.tid; i < n; i += t.stride) {
     int32_t p = x[i];
     p = p > lo ? p : lo;
     y[i] = (uint8_t)(p < hi ? p : hi);
@@ -690,9 +599,8 @@ QuantizedConcatCopyKernel(StfQuantConcatArgs a,
   __syncthreads();
   const uint8_t* __restrict__ src = a.src[k];
   uint8_t* __restrict__ dst = y + a.off[k];
-  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = tid; i < units; i += stride) {
+  GridThread t = ThisThread();
+  for (int64_t i = t.tid; i < units; i += t.stride) {
     int64_t row = i / width, col = i - row * width;
     if (VEC) {
       uint4 v = ((const uint4*)src)[i];
@@ -717,6 +625,23 @@ hipError_t MinMaxI32(const int32_t* x, int32_t* lohi, int64_t n,
   if (n > 0)
     hipLaunchKernelGGL(MinMaxI32Kernel, ElemwiseGrid(n), dim3(256), 0, stream,
                        x, lohi, n);
+  return hipGetLastError();
+}
+
+template <template <int> class Reducer>
+hipError_t QuantizedPool(const uint8_t* x, const float* mn, const float* mx,
+                         uint8_t* y, float* out_mn, float* out_mx,
+                         const StfPoolGeom* gp, hipStream_t stream) {
+  const StfPoolGeom g = *gp;
+  int64_t total = (int64_t)g.N * g.P * g.Q * g.C;
+  if (g.C > 0 && g.C % 16 == 0)
+    hipLaunchKernelGGL((QuantizedPoolKernel<Reducer, 16>),
+                       ElemwiseGrid(total / 16, 256, 1), dim3(256), 0, stream,
+                       x, mn, mx, y, out_mn, out_mx, g, total / 16);
+  else
+    hipLaunchKernelGGL((QuantizedPoolKernel<Reducer, 1>),
+                       ElemwiseGrid(total, 256, 1), dim3(256), 0, stream, x,
+                       mn, mx, y, out_mn, out_mx, g, total);
   return hipGetLastError();
 }
 
@@ -812,17 +737,7 @@ extern "C" hipError_t stf_quantized_max_pool(const uint8_t* x,
                                              float* out_mx,
                                              const StfPoolGeom* gp,
                                              hipStream_t stream) {
-  const StfPoolGeom g = *gp;
-  int64_t total = (int64_t)g.N * g.P * g.Q * g.C;
-  if (g.C > 0 && g.C % 16 == 0)
-    hipLaunchKernelGGL(QuantizedMaxPoolV16Kernel,
-                       ElemwiseGrid(total / 16, 256, 1), dim3(256), 0,
-                       stream, x, mn, mx, y, out_mn, out_mx, g, total / 16);
-  else
-    hipLaunchKernelGGL(QuantizedMaxPoolKernel, ElemwiseGrid(total, 256, 1),
-                       dim3(256), 0, stream, x, mn, mx, y, out_mn, out_mx, g,
-                       total);
-  return hipGetLastError();
+  return QuantizedPool<PoolMax>(x, mn, mx, y, out_mn, out_mx, gp, stream);
 }
 
 extern "C" hipError_t stf_quantized_avg_pool(const uint8_t* x,
@@ -831,17 +746,7 @@ extern "C" hipError_t stf_quantized_avg_pool(const uint8_t* x,
                                              float* out_mx,
                                              const StfPoolGeom* gp,
                                              hipStream_t stream) {
-  const StfPoolGeom g = *gp;
-  int64_t total = (int64_t)g.N * g.P * g.Q * g.C;
-  if (g.C > 0 && g.C % 16 == 0)
-    hipLaunchKernelGGL(QuantizedAvgPoolV16Kernel,
-                       ElemwiseGrid(total / 16, 256, 1), dim3(256), 0,
-                       stream, x, mn, mx, y, out_mn, out_mx, g, total / 16);
-  else
-    hipLaunchKernelGGL(QuantizedAvgPoolKernel, ElemwiseGrid(total, 256, 1),
-                       dim3(256), 0, stream, x, mn, mx, y, out_mn, out_mx, g,
-                       total);
-  return hipGetLastError();
+  return QuantizedPool<PoolAvg>(x, mn, mx, y, out_mn, out_mx, gp, stream);
 }
 
 extern "C" hipError_t stf_quantized_relu6(const uint8_t* x, const float* mn,

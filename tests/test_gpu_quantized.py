@@ -113,6 +113,22 @@ def test_quantized_matmul(sess, shape, fill):
     assert outs[0].shape == (m, n) and outs[0].dtype == np.int32
 
 
+@pytest.mark.parametrize('a_shape, b_shape, match', [
+    ((2, 3), (4, 2), 'inner dim'), ((3,), (3, 2), 'matrices')])
+def test_quantized_matmul_rejects_bad_shapes(sess, a_shape, b_shape, match):
+    """The shape check fails the op before any kernel is launched."""
+    pa = tf.placeholder(tf.uint8, a_shape)
+    pb = tf.placeholder(tf.uint8, b_shape)
+    with tf.device('/gpu:0'):
+        out = q.quantized_matmul(pa, pb, 0.0, 1.0, 0.0, 1.0)[0]
+    # a session of its own, on the module's graph (hence the fixture): the
+    # failed run must not be the shared session's
+    with _sess() as s:
+        with pytest.raises(tf.errors.InvalidArgumentError, match=match):
+            s.run(out, {pa: np.zeros(a_shape, np.uint8),
+                        pb: np.zeros(b_shape, np.uint8)})
+
+
 # ---------------------------------------------------------------------------
 # QuantizedConv2D
 # ---------------------------------------------------------------------------

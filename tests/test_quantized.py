@@ -1,6 +1,7 @@
 """Quantized ops (csrc/kernels/cpu_quantized.cc; reference quantize_op.cc /
 quantized_matmul_op.cc analogs; quint8/qint32 carried as uint8/int32)."""
 import numpy as np
+import pytest
 
 import simple_tensorflow_amd as tf
 from simple_tensorflow_amd.python.ops import quantized_ops as q
@@ -42,6 +43,19 @@ def test_quantized_matmul_matches_float():
     want = A @ B
     # quint8 quantization noise: ~K * step_a * step_b accumulation error
     assert np.abs(got - want).max() < 0.2
+
+
+@pytest.mark.parametrize('a_shape, b_shape, match', [
+    ((2, 3), (4, 2), 'inner dim'), ((3,), (3, 2), 'matrices')])
+def test_quantized_matmul_rejects_bad_shapes(a_shape, b_shape, match):
+    pa = tf.placeholder(tf.uint8, a_shape)
+    pb = tf.placeholder(tf.uint8, b_shape)
+    with tf.device('/cpu:0'):
+        out = q.quantized_matmul(pa, pb, 0.0, 1.0, 0.0, 1.0)[0]
+    with tf.Session() as s:
+        with pytest.raises(tf.errors.InvalidArgumentError, match=match):
+            s.run(out, {pa: np.zeros(a_shape, np.uint8),
+                        pb: np.zeros(b_shape, np.uint8)})
 
 
 def test_quantized_relu():

@@ -297,7 +297,9 @@ def test_quantized_bias_add_rejects_a_channel_mismatch():
 
 
 # (image H = W, ksize, stride, padding)
-POOL_CASES = [(8, 2, 2, 'VALID'), (7, 3, 2, 'SAME'), (2, 3, 1, 'SAME')]
+# 9x9 under a 7x7 SAME window: the clipped windows are 4, 6 and 7 taps wide
+POOL_CASES = [(8, 2, 2, 'VALID'), (7, 3, 2, 'SAME'), (2, 3, 1, 'SAME'),
+              (9, 7, 2, 'SAME')]
 POOL_CHANNELS = (1, 16, 20, 48)
 
 

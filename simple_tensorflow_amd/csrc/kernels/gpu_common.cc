@@ -42,7 +42,8 @@ int PickSplitK(int64_t M, int64_t N, int64_t K) {
 // Every split-K GEMM atomically accumulates into the arena and the fused
 // cast-and-rezero epilogue restores the all-zero invariant while draining
 // the result — the per-GEMM hipMemset launch disappears. All compute runs
-// on one stream, so consecutive uses are ordered; growth leaks the old
+// on one stream and SplitKInto enqueues each use's accumulation and drain
+// under one lock, so consecutive uses are ordered; growth leaks the old
 // buffer deliberately (in-flight work and captured hipGraphs may still
 // reference it).
 float* SplitKArena(int ordinal, int64_t elems, hipStream_t s) {
@@ -78,11 +79,19 @@ hipError_t SplitKInto(OpKernelContext* ctx, int64_t elems,
                       const std::function<hipError_t(float*)>& launch,
                       void* out_bf16) {
   hipStream_t s = GPU_STREAM(ctx);
+  // The executor runs independent ops on pool threads, all enqueueing on
+  // the one compute stream. The accumulation and the drain that re-zeroes
+  // the arena must reach the stream back to back: were another split-K
+  // op's accumulation enqueued between them, the first drain would hand out
+  // the sum of both and the second one zeros. Held for two enqueues only.
+  static std::mutex enqueue_mu;
+  std::unique_lock<std::mutex> l(enqueue_mu);
   if (float* arena = SplitKArena(ctx->device()->gpu_ordinal(), elems, s)) {
     hipError_t e = launch(arena);
     if (e != hipSuccess) return e;
     return stf_cast_f32_bf16_zero(arena, out_bf16, elems, s);
   }
+  l.unlock();
   Tensor scratch = ctx->allocate_temp(DT_FLOAT, TensorShape({elems}));
   hipError_t e = ZeroF32(scratch.raw_data(), elems, s);
   if (e != hipSuccess) return e;

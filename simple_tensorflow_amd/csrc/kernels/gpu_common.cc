@@ -25,7 +25,10 @@ int PickSplitK(int64_t M, int64_t N, int64_t K) {
     want = 512 / (tiles ? tiles : 1);
     // Very skinny outputs with huge K (the 7x7 stem dW: 392x64x3.2M):
     // deepen the split to ~2048 blocks (sweep: 3.14ms @1044 blocks ->
-    // 2.39ms @2048; flat beyond). Keep >=48 K-chunks per block.
+    // 2.39ms @2048; flat beyond). Keep >=48 K-chunks per block. The ResNet
+    // stem itself (cout 64) no longer comes here: its dW runs on
+    // stf_conv2d_dw_tall, which does not split by this function. Other
+    // skinny huge-K shapes still do.
     int64_t kt = K / 64;
     if (tiles <= 6 && kt / (tiles * want) > 96) {
       want = 2048 / tiles;

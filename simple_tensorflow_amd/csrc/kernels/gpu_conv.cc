@@ -279,7 +279,11 @@ REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropInputAdd").Device(DEVICE_GPU).TypeCo
 class GpuConv2DBackpropFilterOp : public OpKernel {
  public:
   explicit GpuConv2DBackpropFilterOp(OpKernelConstruction* c)
-      : OpKernel(c), attrs_(c) {}
+      : OpKernel(c), attrs_(c) {
+    // STF_NO_TALL_DW (A/B runs) keeps every dW on the split-K GEMM. Read per
+    // kernel, so a new graph sees a changed setting.
+    tall_dw_ = getenv("STF_NO_TALL_DW") == nullptr;
+  }
   void Compute(OpKernelContext* ctx) override {
     hipStream_t s = GPU_STREAM(ctx);
     // ---- geometry ----
@@ -324,8 +328,15 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
         xdata = xp.raw_data();
         out = dwp.raw_data();
       }
-      int sk = PickSplitK(gi.RSC(), g.K, g.M());
+      // cout 64 with a short filter (ResNet's stem and stage-2 3x3): one
+      // block holds all of dW and x and dy are streamed once, instead of
+      // split-K over the im2col expansion.
+      bool tall = tall_dw_ && stf_conv2d_dw_tall_ok(&si);
+      int sk = tall ? 0 : PickSplitK(gi.RSC(), g.K, g.M());
       OP_HIP_OK(ctx, SplitKInto(ctx, gi.RSC() * g.K, [&](float* acc) {
+        if (tall)
+          return stf_conv2d_dw_tall(xdata, dy.raw_data(), acc, ZeroPage(),
+                                    &si, s);
         return stf_conv2d_dw_splitk(xdata, dy.raw_data(), acc, ZeroPage(),
                                     &si, sk, s);
       }, out));
@@ -357,6 +368,7 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
 
  private:
   ConvAttrs attrs_;
+  bool tall_dw_;
 };
 REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropFilter").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("filter_sizes"), GpuConv2DBackpropFilterOp);
 

@@ -112,6 +112,23 @@ hipError_t stf_conv2d_dx_8ph(const void* dy, const void* wt, void* dx,
                              const StfConvGeom* g, int64_t rscp,
                              hipStream_t stream);
 
+// ---- conv_dw_tall.hip ----
+// Backprop-filter of a cout = 64 convolution with one block holding the whole
+// [r*s*c, 64] f32 output: adds into the zeroed dw_f32 with atomics, like
+// stf_conv2d_dw_splitk. The gate (stf_conv2d_dw_tall_ok): cout == 64,
+// c % 8 == 0, r*s*c <= 576, n*p*q % 64 == 0, n*p*q >= 768, and three LDS
+// buffers of 16 * (roundup(r * (31*sw + s) * c/8, 256) + 256) bytes within
+// 160 KiB (and one image's h*w*c below 2^31).
+int stf_conv2d_dw_tall_ok(const StfConvGeom* g);
+hipError_t stf_conv2d_dw_tall(const void* x, const void* dy, void* dw_f32,
+                              const void* zero16, const StfConvGeom* g,
+                              hipStream_t stream);
+// Test hook for the kernel's transposing LDS fragment read: tile is device
+// u16 [32 k][16 rows]; out is device u16 [64 lanes][8], the MFMA operand
+// register of each lane (row = lane % 16, k = 8 * (lane / 16) + 0..7).
+hipError_t stf_conv2d_dw_tall_frag_probe(const void* tile_u16, void* out_u16,
+                                         hipStream_t stream);
+
 // ---- gemm_i8.hip ----
 // Quantized quint8 x quint8 -> qint32 on the i8 MFMA. Ranges are device f32
 // scalars: zero points are derived on the device, min_out/max_out are

@@ -18,6 +18,7 @@
 #include "core/protos.h"
 #include "util/table.h"
 #include "framework/op.h"
+#include "kernels/hip/stf_kernels.h"
 #include "runtime/session.h"
 
 namespace py = pybind11;
@@ -627,6 +628,27 @@ PYBIND11_MODULE(_core, m) {
     // Probe: capture with cross-thread enqueue + an in-capture hipMalloc —
     // mirrors what the executor does during a captured step.
     return stf::HipGraphSelfTest();
+  });
+  m.def("conv_dw_tall_frag_probe", [](py::array_t<uint16_t> tile) {
+    // The transposing LDS fragment read of hip/conv_dw_tall.hip on one
+    // [32 k][16 rows] tile: returns [64 lanes][8], each lane's MFMA operand.
+    if (tile.size() != 32 * 16) throw std::runtime_error("tile: 32x16 u16");
+    auto in = py::array_t<uint16_t, py::array::c_style |
+                                        py::array::forcecast>(tile);
+    py::array_t<uint16_t> out({64, 8});
+    void* dev = nullptr;
+    auto ok = [&](hipError_t e) {
+      if (e == hipSuccess) return;
+      if (dev) (void)hipFree(dev);
+      throw std::runtime_error(hipGetErrorString(e));
+    };
+    ok(hipMalloc(&dev, 2048));
+    ok(hipMemcpy(dev, in.data(), 1024, hipMemcpyHostToDevice));
+    ok(stf_conv2d_dw_tall_frag_probe(dev, (char*)dev + 1024, nullptr));
+    ok(hipMemcpy(out.mutable_data(), (char*)dev + 1024, 1024,
+                 hipMemcpyDeviceToHost));
+    (void)hipFree(dev);
+    return out;
   });
   m.def("rccl_get_unique_id", []() {
     return py::bytes(stf::RcclGetUniqueId());

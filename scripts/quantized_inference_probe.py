@@ -16,6 +16,14 @@ lengths are timed in three alternating rounds; the table gives the median
 over the rounds, and the lowest and highest round as the spread against
 which a ratio is to be read.
 
+With --fused it times one quantized layer instead, and nothing else: the
+chain QuantizedConv2D -> Requantize -> QuantizedBiasAdd -> Requantize ->
+QuantizedRelu (constant requested ranges) against the one
+QuantizedConv2DWithBiasAndRequantize, at the shape above with a 3x3x64x64
+filter, with the bf16 Conv2D beside them for orientation; and the same pair
+for a MatMul at (256*14*14, 256, 2304). The chain, the fused op and the bf16
+op take turns inside each of five rounds.
+
 Needs a GPU; run it under a time limit:
   timeout 600 python scripts/quantized_inference_probe.py
 """
@@ -113,16 +121,126 @@ def _cases():
     ]
 
 
+# ---------------------------------------------------------------------------
+# --fused: one quantized layer as the chain of five ops against the fused op
+# ---------------------------------------------------------------------------
+GEMM = (256 * 14 * 14, 256, 2304)  # quantized_gemm_probe.py's stage shape
+REQ = (-8.0, 8.0)                   # the constant requested range
+
+
+def _layer_chain(acc):
+    """Requantize -> QuantizedBiasAdd -> Requantize -> QuantizedRelu behind
+    the qint32 triple acc, with constant requested ranges."""
+    def make(b8, bmn, bmx):
+        c8, mn, mx = q.requantize(acc[0], acc[1], acc[2], REQ[0], REQ[1])
+        s32, smn, smx = q.quantized_bias_add(c8, b8, mn, mx, bmn, bmx)
+        s8, mn, mx = q.requantize(s32, smn, smx, REQ[0], REQ[1])
+        return q.quantized_relu(s8, mn, mx)[0]
+    return make
+
+
+def _fused_cases():
+    """(case, chain, fused op, bf16 op or None)."""
+    m, n, k = GEMM
+    with tf.device('/gpu:0'):
+        x = tf.Variable(tf.random_uniform(SHAPE, -1.0, 1.0))
+        w = tf.Variable(tf.random_uniform(FILTER, -1.0, 1.0))
+        b = tf.Variable(tf.random_uniform((FILTER[3],), -1.0, 1.0))
+        a = tf.Variable(tf.random_uniform((m, k), -1.0, 1.0))
+        wm = tf.Variable(tf.random_uniform((k, n), -1.0, 1.0))
+        bm = tf.Variable(tf.random_uniform((n,), -1.0, 1.0))
+        x8, w8, b8 = [q.quantize_v2(t, -1.0, 1.0) for t in (x, w, b)]
+        a8, wm8, bm8 = [q.quantize_v2(t, -1.0, 1.0) for t in (a, wm, bm)]
+        x16, w16 = tf.cast(x, tf.bfloat16), tf.cast(w, tf.bfloat16)
+
+    def conv_chain():
+        acc = q.quantized_conv2d(x8[0], w8[0], x8[1], x8[2], w8[1], w8[2],
+                                 [1, 1, 1, 1], 'SAME')
+        return _layer_chain(acc)(*b8)
+
+    def conv_fused():
+        return q.quantized_conv2d_with_bias_and_requantize(
+            x8[0], w8[0], b, x8[1], x8[2], w8[1], w8[2], REQ[0], REQ[1],
+            [1, 1, 1, 1], 'SAME', activation='Relu')[0]
+
+    def matmul_chain():
+        acc = q.quantized_matmul(a8[0], wm8[0], a8[1], a8[2], wm8[1], wm8[2])
+        return _layer_chain(acc)(*bm8)
+
+    def matmul_fused():
+        return q.quantized_matmul_with_bias_and_requantize(
+            a8[0], wm8[0], bm, a8[1], a8[2], wm8[1], wm8[2], REQ[0], REQ[1],
+            activation='Relu')[0]
+
+    return [('conv %s * %s' % (SHAPE, FILTER), conv_chain, conv_fused,
+             lambda: tf.nn.conv2d(x16, w16, [1, 1, 1, 1], 'SAME')),
+            ('matmul %dx%dx%d' % GEMM, matmul_chain, matmul_fused, None)]
+
+
+def _alternating(sess, makes, lo, hi, warmup, iters, rounds=5):
+    """Per-op seconds of each make, one list per make with a value per
+    round; the makes take turns inside every round."""
+    ops = []
+    for make in makes:
+        with tf.device('/gpu:0'):
+            ops.append((_chained(make, lo), _chained(make, hi)))
+    per_op = [[] for _ in makes]
+    for _ in range(rounds):
+        for i, (op_lo, op_hi) in enumerate(ops):
+            t_lo = _median_step(sess, op_lo, warmup, iters)
+            t_hi = _median_step(sess, op_hi, warmup, iters)
+            per_op[i].append((t_hi - t_lo) / (hi - lo))
+    return per_op
+
+
+def _fused_main(sess, args):
+    cases = _fused_cases()
+    sess.run(tf.global_variables_initializer())
+    if args.profile:  # for a kernel trace: a few runs of each, no timing
+        for _, chain, fused, _ in cases:
+            for make in (chain, fused):
+                with tf.device('/gpu:0'):
+                    op = _chained(make, 4)
+                for _ in range(3):
+                    sess.run(op)
+                sess.sync()
+        return
+    print('| case | five-op chain us (rounds) | fused op us (rounds) | '
+          'chain / fused (rounds) | bf16 us |')
+    print('|---|---|---|---|---|')
+    for case, chain, fused, bf16 in cases:
+        makes = [chain, fused] + ([bf16] if bf16 else [])
+        t = _alternating(sess, makes, args.lo, args.hi, args.warmup,
+                         args.iters)
+        us = [[v * 1e6 for v in r] for r in t]
+        ratio = [c / f for c, f in zip(us[0], us[1])]
+        print('| %s | %.1f (%.1f-%.1f) | %.1f (%.1f-%.1f) | '
+              '%.2f (%.2f-%.2f) | %s |'
+              % (case, np.median(us[0]), min(us[0]), max(us[0]),
+                 np.median(us[1]), min(us[1]), max(us[1]), np.median(ratio),
+                 min(ratio), max(ratio),
+                 '%.1f' % np.median(us[2]) if bf16 else '-'), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--lo', type=int, default=4)
     ap.add_argument('--hi', type=int, default=44)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--fused', action='store_true',
+                    help='time one quantized layer as the chain of five ops '
+                         'against the fused op, and nothing else')
+    ap.add_argument('--profile', action='store_true',
+                    help='with --fused: run the chain and the fused op a few '
+                         'times and exit, for rocprofv3 --kernel-trace '
+                         '--stats in a run of its own')
     args = ap.parse_args()
 
     sess = tf.Session()
     assert sess.num_gpus() > 0, 'the probe needs a GPU'
+    if args.fused:
+        return _fused_main(sess, args)
     cases = _cases()
     sess.run(tf.global_variables_initializer())
 

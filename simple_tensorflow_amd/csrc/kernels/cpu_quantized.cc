@@ -79,110 +79,213 @@ class DequantizeOp : public OpKernel {
 };
 REGISTER_KERNEL_BUILDER(Name("Dequantize").Device(DEVICE_CPU), DequantizeOp);
 
+// The accumulation of QuantizedMatMul and of its fused form:
+// sink(index into the [M, N] output, n, sum_k (a - za)(b - zb) wrapped to 32
+// bit) for every output element.
+template <class Sink>
+void QuantMatMulLoop(const uint8_t* ap, const uint8_t* bp, int64_t M,
+                     int64_t N, int64_t K, bool ta, bool tb, int32_t za,
+                     int32_t zb, Sink sink) {
+  for (int64_t m = 0; m < M; ++m)
+    for (int64_t n = 0; n < N; ++n) {
+      int64_t acc = 0;
+      for (int64_t k = 0; k < K; ++k) {
+        int32_t av = ta ? ap[k * M + m] : ap[m * K + k];
+        int32_t bv = tb ? bp[n * K + k] : bp[k * N + n];
+        acc += (int64_t)(av - za) * (bv - zb);
+      }
+      sink(m * N + n, n, (int32_t)acc);
+    }
+}
+
+// The fused epilogue as an accumulation sink (kernels/quantized_util.h).
+template <int ACT>
+struct QuantFusedSink {
+  uint8_t* out;
+  const float* bias;
+  QuantFusedScale sc;
+  void operator()(int64_t i, int64_t c, int32_t acc) const {
+    out[i] = QuantFusedU8<ACT>(acc, bias[c], sc);
+  }
+};
+
+// run(sink) with the sink of the activation act.
+template <class Run>
+void WithQuantFusedSink(int act, uint8_t* out, const float* bias,
+                        const QuantFusedScale& sc, Run run) {
+  if (act == kQuantActRelu6)
+    run(QuantFusedSink<kQuantActRelu6>{out, bias, sc});
+  else if (act == kQuantActRelu)
+    run(QuantFusedSink<kQuantActRelu>{out, bias, sc});
+  else
+    run(QuantFusedSink<kQuantActNone>{out, bias, sc});
+}
+
 // out_int32 = sum (a_q - a_zero) * (b_q - b_zero) in float-equivalent units:
 // we accumulate raw products and propagate the float range exactly as the
 // reference does (min/max of the int32 result in float units).
+// QuantizedMatMulWithBiasAndRequantize (fused) sends the same sums through
+// the fused epilogue instead: inputs a, b, bias, the four ranges, the
+// requested output range; quint8 out.
 class QuantizedMatMulOp : public OpKernel {
  public:
-  explicit QuantizedMatMulOp(OpKernelConstruction* c) : OpKernel(c) {
+  QuantizedMatMulOp(OpKernelConstruction* c, bool fused)
+      : OpKernel(c), fused_(fused) {
     c->GetAttr("transpose_a", &ta_);
     c->GetAttr("transpose_b", &tb_);
+    if (fused_) act_ = QuantFusedActivation(c);
   }
+  explicit QuantizedMatMulOp(OpKernelConstruction* c)
+      : QuantizedMatMulOp(c, false) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& a = ctx->input(0);
     const Tensor& b = ctx->input(1);
-    float min_a = RangeIn(ctx, 2);
-    float max_a = RangeIn(ctx, 3);
-    float min_b = RangeIn(ctx, 4);
-    float max_b = RangeIn(ctx, 5);
+    int r = fused_ ? 3 : 2;  // the first range input
+    float min_a = RangeIn(ctx, r);
+    float max_a = RangeIn(ctx, r + 1);
+    float min_b = RangeIn(ctx, r + 2);
+    float max_b = RangeIn(ctx, r + 3);
     int64_t M, N, K;
     OP_REQUIRES_OK(ctx,
                    QuantMatMulDims(a.shape(), b.shape(), ta_, tb_, &M, &N, &K));
+    if (fused_)
+      OP_REQUIRES_OK(ctx, QuantFusedBiasDims(def().op, ctx->input(2).shape(),
+                                             N));
     Tensor* out = ctx->allocate_output(0, TensorShape({M, N}));
     const uint8_t* ap = a.flat<uint8_t>();
     const uint8_t* bp = b.flat<uint8_t>();
-    int32_t* op = out->flat<int32_t>();
     // zero points for MIN_COMBINED quint8
     float sa = QuantStep(min_a, max_a);
     float sb = QuantStep(min_b, max_b);
     int32_t za = QuantZeroPoint(min_a, max_a);
     int32_t zb = QuantZeroPoint(min_b, max_b);
-    for (int64_t m = 0; m < M; ++m)
-      for (int64_t n = 0; n < N; ++n) {
-        int64_t acc = 0;
-        for (int64_t k = 0; k < K; ++k) {
-          int32_t av = ta_ ? ap[k * M + m] : ap[m * K + k];
-          int32_t bv = tb_ ? bp[n * K + k] : bp[k * N + n];
-          acc += (int64_t)(av - za) * (bv - zb);
-        }
-        op[m * N + n] = (int32_t)acc;
-      }
+    if (fused_) {
+      QuantFusedScale sc = MakeQuantFusedScale(
+          min_a, max_a, min_b, max_b, RangeIn(ctx, 7), RangeIn(ctx, 8));
+      WithQuantFusedSink(act_, out->flat<uint8_t>(),
+                         ctx->input(2).flat<float>(), sc, [&](auto sink) {
+                           QuantMatMulLoop(ap, bp, M, N, K, ta_, tb_, za, zb,
+                                           sink);
+                         });
+      RangeOut(ctx, 1, sc.mn, sc.mx);
+      return;
+    }
+    int32_t* op = out->flat<int32_t>();
+    QuantMatMulLoop(ap, bp, M, N, K, ta_, tb_, za, zb,
+                    [op](int64_t i, int64_t, int32_t acc) { op[i] = acc; });
     // float value of one output unit = sa * sb; int32 range maps to:
     RangeOut(ctx, 1, QuantProductMin(sa, sb), QuantProductMax(sa, sb));
   }
 
  private:
+  bool fused_;
   bool ta_ = false, tb_ = false;
+  int act_ = 0;
+};
+class QuantizedMatMulFusedOp : public QuantizedMatMulOp {
+ public:
+  explicit QuantizedMatMulFusedOp(OpKernelConstruction* c)
+      : QuantizedMatMulOp(c, true) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedMatMul").Device(DEVICE_CPU),
                         QuantizedMatMulOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedMatMulWithBiasAndRequantize").Device(DEVICE_CPU),
+    QuantizedMatMulFusedOp);
 
 // out[n,p,q,k] = sum over the taps inside the image of
 // (x - z_in) * (w - z_f), NHWC input, [R,S,C,K] filter, reduced to int32
 // modulo 2^32 (reference quantized_conv_ops.cc analog). Zero points and the
 // output range follow QuantizedMatMul.
+// QuantizedConv2DWithBiasAndRequantize (fused) sends the same sums through
+// the fused epilogue: inputs input, filter, bias, the four ranges, the
+// requested output range; quint8 output.
+template <class Sink>
+void QuantConvLoop(const ConvGeom& g, const uint8_t* xp, const uint8_t* wp,
+                   int32_t zx, int32_t zf, Sink sink) {
+  std::vector<int64_t> acc(g.K);
+  for (int64_t n = 0; n < g.N; ++n)
+    for (int64_t p = 0; p < g.P; ++p)
+      for (int64_t q = 0; q < g.Q; ++q) {
+        std::fill(acc.begin(), acc.end(), 0);
+        for (int64_t r = 0; r < g.R; ++r) {
+          int64_t h = p * g.sh - g.ph + r;
+          if (h < 0 || h >= g.H) continue;
+          for (int64_t s = 0; s < g.S; ++s) {
+            int64_t wi = q * g.sw - g.pw + s;
+            if (wi < 0 || wi >= g.W) continue;
+            const uint8_t* xr = xp + ((n * g.H + h) * g.W + wi) * g.C;
+            const uint8_t* wr = wp + (r * g.S + s) * g.C * g.K;
+            for (int64_t c = 0; c < g.C; ++c) {
+              int64_t xv = (int32_t)xr[c] - zx;
+              for (int64_t k = 0; k < g.K; ++k)
+                acc[k] += xv * ((int32_t)wr[c * g.K + k] - zf);
+            }
+          }
+        }
+        int64_t o = ((n * g.P + p) * g.Q + q) * g.K;
+        for (int64_t k = 0; k < g.K; ++k) sink(o + k, k, (int32_t)acc[k]);
+      }
+}
+
 class QuantizedConv2DOp : public OpKernel {
  public:
+  QuantizedConv2DOp(OpKernelConstruction* c, bool fused)
+      : OpKernel(c), fused_(fused), attrs_(c) {
+    if (fused_) act_ = QuantFusedActivation(c);
+  }
   explicit QuantizedConv2DOp(OpKernelConstruction* c)
-      : OpKernel(c), attrs_(c) {}
+      : QuantizedConv2DOp(c, false) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& w = ctx->input(1);
     ConvGeom g;
     OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g));
-    float min_x = RangeIn(ctx, 2);
-    float max_x = RangeIn(ctx, 3);
-    float min_w = RangeIn(ctx, 4);
-    float max_w = RangeIn(ctx, 5);
+    if (fused_)
+      OP_REQUIRES_OK(ctx, QuantFusedBiasDims(attrs_.op,
+                                             ctx->input(2).shape(), g.K));
+    int r = fused_ ? 3 : 2;  // the first range input
+    float min_x = RangeIn(ctx, r);
+    float max_x = RangeIn(ctx, r + 1);
+    float min_w = RangeIn(ctx, r + 2);
+    float max_w = RangeIn(ctx, r + 3);
     Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.K}));
     const uint8_t* xp = x.flat<uint8_t>();
     const uint8_t* wp = w.flat<uint8_t>();
-    int32_t* op = out->flat<int32_t>();
     float sx = QuantStep(min_x, max_x);
     float sf = QuantStep(min_w, max_w);
     int32_t zx = QuantZeroPoint(min_x, max_x);
     int32_t zf = QuantZeroPoint(min_w, max_w);
-    std::vector<int64_t> acc(g.K);
-    for (int64_t n = 0; n < g.N; ++n)
-      for (int64_t p = 0; p < g.P; ++p)
-        for (int64_t q = 0; q < g.Q; ++q) {
-          std::fill(acc.begin(), acc.end(), 0);
-          for (int64_t r = 0; r < g.R; ++r) {
-            int64_t h = p * g.sh - g.ph + r;
-            if (h < 0 || h >= g.H) continue;
-            for (int64_t s = 0; s < g.S; ++s) {
-              int64_t wi = q * g.sw - g.pw + s;
-              if (wi < 0 || wi >= g.W) continue;
-              const uint8_t* xr = xp + ((n * g.H + h) * g.W + wi) * g.C;
-              const uint8_t* wr = wp + (r * g.S + s) * g.C * g.K;
-              for (int64_t c = 0; c < g.C; ++c) {
-                int64_t xv = (int32_t)xr[c] - zx;
-                for (int64_t k = 0; k < g.K; ++k)
-                  acc[k] += xv * ((int32_t)wr[c * g.K + k] - zf);
-              }
-            }
-          }
-          int32_t* o = op + ((n * g.P + p) * g.Q + q) * g.K;
-          for (int64_t k = 0; k < g.K; ++k) o[k] = (int32_t)acc[k];
-        }
+    if (fused_) {
+      QuantFusedScale sc = MakeQuantFusedScale(
+          min_x, max_x, min_w, max_w, RangeIn(ctx, 7), RangeIn(ctx, 8));
+      WithQuantFusedSink(
+          act_, out->flat<uint8_t>(), ctx->input(2).flat<float>(), sc,
+          [&](auto sink) { QuantConvLoop(g, xp, wp, zx, zf, sink); });
+      RangeOut(ctx, 1, sc.mn, sc.mx);
+      return;
+    }
+    int32_t* op = out->flat<int32_t>();
+    QuantConvLoop(g, xp, wp, zx, zf,
+                  [op](int64_t i, int64_t, int32_t acc) { op[i] = acc; });
     RangeOut(ctx, 1, QuantProductMin(sx, sf), QuantProductMax(sx, sf));
   }
 
  private:
+  bool fused_;
   ConvAttrs attrs_;
+  int act_ = 0;
+};
+class QuantizedConv2DFusedOp : public QuantizedConv2DOp {
+ public:
+  explicit QuantizedConv2DFusedOp(OpKernelConstruction* c)
+      : QuantizedConv2DOp(c, true) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_CPU),
                         QuantizedConv2DOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedConv2DWithBiasAndRequantize").Device(DEVICE_CPU),
+    QuantizedConv2DFusedOp);
 
 class QuantizedReluOp : public OpKernel {
  public:

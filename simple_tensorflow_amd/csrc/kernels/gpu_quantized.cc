@@ -1,8 +1,10 @@
 // GPU OpKernels: the quantized family (QuantizeV2, Dequantize,
-// QuantizedMatMul, QuantizedConv2D, QuantizedRelu, RequantizationRange,
+// QuantizedMatMul, QuantizedConv2D, their fused forms
+// Quantized{MatMul,Conv2D}WithBiasAndRequantize, QuantizedRelu,
+// RequantizationRange,
 // QuantizeDownAndShrinkRange, Requantize, QuantizedBiasAdd,
 // QuantizedMaxPool, QuantizedAvgPool, QuantizedRelu6, QuantizedConcat) on
-// kernels/hip/gemm_i8.hip and kernels/hip/quantized.hip.
+// kernels/hip/gemm_i8.hip, gemm_i8_fused.hip and quantized.hip.
 //
 // The min/max ranges live in device memory on both sides of every op: only
 // QuantizedConcat's axis is in host memory and nothing here reads a range
@@ -75,12 +77,19 @@ hipError_t Pack(OpKernelContext* ctx, const void* src, int64_t sr, int64_t sk,
   return stf_pack_i8(src, sr, sk, rows, K, packed->raw_data(), sp, taps, s);
 }
 
+// QuantizedMatMul, and with fused QuantizedMatMulWithBiasAndRequantize: the
+// same operand preparation in front of the fused kernel. Its inputs are a,
+// b, bias, the four ranges, the requested output range.
 class GpuQuantizedMatMulOp : public OpKernel {
  public:
-  explicit GpuQuantizedMatMulOp(OpKernelConstruction* c) : OpKernel(c) {
+  GpuQuantizedMatMulOp(OpKernelConstruction* c, bool fused)
+      : OpKernel(c), fused_(fused) {
     c->GetAttr("transpose_a", &ta_);
     c->GetAttr("transpose_b", &tb_);
+    if (fused_) act_ = QuantFusedActivation(c);
   }
+  explicit GpuQuantizedMatMulOp(OpKernelConstruction* c)
+      : GpuQuantizedMatMulOp(c, false) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& a = ctx->input(0);
     const Tensor& b = ctx->input(1);
@@ -88,6 +97,10 @@ class GpuQuantizedMatMulOp : public OpKernel {
     int64_t M, N, K;
     OP_REQUIRES_OK(ctx,
                    QuantMatMulDims(a.shape(), b.shape(), ta_, tb_, &M, &N, &K));
+    if (fused_)
+      OP_REQUIRES_OK(ctx, QuantFusedBiasDims(def().op, ctx->input(2).shape(),
+                                             N));
+    int r = fused_ ? 3 : 2;  // the first range input
     Tensor* out = ctx->allocate_output(0, TensorShape({M, N}));
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
@@ -105,24 +118,50 @@ class GpuQuantizedMatMulOp : public OpKernel {
                           1, &a_packed, nullptr, s));
       ap = a_packed.raw_data();
     }
+    if (fused_) {
+      OP_HIP_OK(ctx, stf_gemm_i8_fused(
+                         ap, pack_a ? 1 : 0, bp.raw_data(),
+                         (const int32_t*)bsums.raw_data(), F32(ctx->input(2)),
+                         F32(ctx->input(r)), F32(ctx->input(r + 1)),
+                         F32(ctx->input(r + 2)), F32(ctx->input(r + 3)),
+                         F32(ctx->input(7)), F32(ctx->input(8)), act_,
+                         (uint8_t*)out->raw_data(), omn, omx, M, N, K, s));
+      return;
+    }
     OP_HIP_OK(ctx, stf_gemm_i8(ap, pack_a ? 1 : 0, bp.raw_data(),
                                (const int32_t*)bsums.raw_data(),
-                               F32(ctx->input(2)), F32(ctx->input(3)),
-                               F32(ctx->input(4)), F32(ctx->input(5)),
+                               F32(ctx->input(r)), F32(ctx->input(r + 1)),
+                               F32(ctx->input(r + 2)), F32(ctx->input(r + 3)),
                                (int32_t*)out->raw_data(), omn, omx, M, N, K,
                                s));
   }
 
  private:
+  bool fused_;
   bool ta_ = false, tb_ = false;
+  int act_ = 0;
+};
+class GpuQuantizedMatMulFusedOp : public GpuQuantizedMatMulOp {
+ public:
+  explicit GpuQuantizedMatMulFusedOp(OpKernelConstruction* c)
+      : GpuQuantizedMatMulOp(c, true) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedMatMul").Device(DEVICE_GPU),
                         GpuQuantizedMatMulOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedMatMulWithBiasAndRequantize").Device(DEVICE_GPU),
+    GpuQuantizedMatMulFusedOp);
 
+// QuantizedConv2D, and with fused QuantizedConv2DWithBiasAndRequantize
+// (inputs: input, filter, bias, the four ranges, the requested range).
 class GpuQuantizedConv2DOp : public OpKernel {
  public:
+  GpuQuantizedConv2DOp(OpKernelConstruction* c, bool fused)
+      : OpKernel(c), fused_(fused), attrs_(c) {
+    if (fused_) act_ = QuantFusedActivation(c);
+  }
   explicit GpuQuantizedConv2DOp(OpKernelConstruction* c)
-      : OpKernel(c), attrs_(c) {}
+      : GpuQuantizedConv2DOp(c, false) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& w = ctx->input(1);
@@ -130,6 +169,10 @@ class GpuQuantizedConv2DOp : public OpKernel {
     ConvGeom cg;
     StfConvGeom g;
     OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &cg, &g));
+    if (fused_)
+      OP_REQUIRES_OK(ctx, QuantFusedBiasDims(attrs_.op,
+                                             ctx->input(2).shape(), cg.K));
+    int r = fused_ ? 3 : 2;  // the first range input
     Tensor* y = ctx->allocate_output(0,
                                      TensorShape({cg.N, cg.P, cg.Q, cg.K}));
     float* omn = ScalarOut(ctx, 1);
@@ -149,18 +192,38 @@ class GpuQuantizedConv2DOp : public OpKernel {
       OP_HIP_OK(ctx, stf_im2col_i8(x.raw_data(), col.raw_data(), &g, kp, s));
       ap = col.raw_data();
     }
+    if (fused_) {
+      OP_HIP_OK(ctx, stf_conv2d_i8_fused(
+                         ap, implicit ? 1 : 0, wp.raw_data(),
+                         (const int32_t*)wsums.raw_data(), F32(ctx->input(2)),
+                         F32(ctx->input(r)), F32(ctx->input(r + 1)),
+                         F32(ctx->input(r + 2)), F32(ctx->input(r + 3)),
+                         F32(ctx->input(7)), F32(ctx->input(8)), act_,
+                         (uint8_t*)y->raw_data(), omn, omx, &g, s));
+      return;
+    }
     OP_HIP_OK(ctx, stf_conv2d_i8(ap, implicit ? 1 : 0, wp.raw_data(),
                                  (const int32_t*)wsums.raw_data(),
-                                 F32(ctx->input(2)), F32(ctx->input(3)),
-                                 F32(ctx->input(4)), F32(ctx->input(5)),
+                                 F32(ctx->input(r)), F32(ctx->input(r + 1)),
+                                 F32(ctx->input(r + 2)), F32(ctx->input(r + 3)),
                                  (int32_t*)y->raw_data(), omn, omx, &g, s));
   }
 
  private:
+  bool fused_;
   ConvAttrs attrs_;
+  int act_ = 0;
+};
+class GpuQuantizedConv2DFusedOp : public GpuQuantizedConv2DOp {
+ public:
+  explicit GpuQuantizedConv2DFusedOp(OpKernelConstruction* c)
+      : GpuQuantizedConv2DOp(c, true) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_GPU),
                         GpuQuantizedConv2DOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedConv2DWithBiasAndRequantize").Device(DEVICE_GPU),
+    GpuQuantizedConv2DFusedOp);
 
 // QuantizedRelu and QuantizedRelu6: two entry points of one signature.
 using QuantizedClampFn = hipError_t (*)(const uint8_t*, const float*,

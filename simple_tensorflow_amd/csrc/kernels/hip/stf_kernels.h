@@ -167,6 +167,30 @@ hipError_t stf_conv2d_i8(const void* x_or_col, int implicit, const void* wp,
                          float* max_out, const StfConvGeom* g,
                          hipStream_t stream);
 
+// ---- gemm_i8_fused.hip ----
+// stf_gemm_i8 and stf_conv2d_i8 with the epilogue fused in, on operands
+// prepared by stf_pack_i8 / stf_im2col_i8: quint8 C = the quantized value,
+// under [req_min, req_max], of activation(acc * step_a * step_b + bias[col])
+// (stf::QuantFusedU8). bias: device f32 [N] / [cout]; req_min, req_max:
+// device f32 scalars; activation: stf::QuantActivation. min_out/max_out get
+// the requested range after QuantizeV2's max <= min rule.
+hipError_t stf_gemm_i8_fused(const void* A, int a_packed, const void* Bp,
+                             const int32_t* bsums, const float* bias,
+                             const float* min_a, const float* max_a,
+                             const float* min_b, const float* max_b,
+                             const float* req_min, const float* req_max,
+                             int activation, uint8_t* C, float* min_out,
+                             float* max_out, int64_t M, int64_t N, int64_t K,
+                             hipStream_t stream);
+hipError_t stf_conv2d_i8_fused(const void* x_or_col, int implicit,
+                               const void* wp, const int32_t* wsums,
+                               const float* bias, const float* min_x,
+                               const float* max_x, const float* min_w,
+                               const float* max_w, const float* req_min,
+                               const float* req_max, int activation,
+                               uint8_t* y, float* min_out, float* max_out,
+                               const StfConvGeom* g, hipStream_t stream);
+
 // ---- quantized.hip ----
 // Bit-equal to the CPU kernels (kernels/cpu_quantized.cc). Ranges are device
 // f32 scalars in and out.

@@ -8,6 +8,7 @@
 
 #include "framework/op_kernel.h"
 #include "kernels/kernel_util.h"
+#include "kernels/quantized_util.h"
 
 namespace stf {
 
@@ -35,6 +36,30 @@ inline Status QuantBiasAddDims(const TensorShape& in, const TensorShape& bias,
   *C = bias.dim_size(0);
   *rows = *C ? in.num_elements() / *C : 0;
   return Status::OK();
+}
+
+// The float bias of the fused conv / matmul ops: one value per output
+// channel (cout, or N of the matmul).
+inline Status QuantFusedBiasDims(const std::string& op,
+                                 const TensorShape& bias, int64_t channels) {
+  if (bias.dims() != 1 || bias.dim_size(0) != channels)
+    return errors::InvalidArgument(op, ": bias must have shape [", channels,
+                                   "], got ", bias.DebugString());
+  return Status::OK();
+}
+
+// The activation attribute of the fused ops -> QuantActivation
+// (kernels/quantized_util.h). Anything else fails the kernel's construction.
+inline QuantActivation QuantFusedActivation(OpKernelConstruction* c) {
+  std::string a;
+  c->GetAttr("activation", &a);
+  if (a == "None") return kQuantActNone;
+  if (a == "Relu") return kQuantActRelu;
+  if (a == "Relu6") return kQuantActRelu6;
+  c->SetStatus(errors::InvalidArgument(
+      c->def().op, ": activation must be None, Relu or Relu6, got '", a,
+      "'"));
+  return kQuantActNone;
 }
 
 // QuantizedConcat of n inputs, each viewed as [outer, row[k]] bytes; input k

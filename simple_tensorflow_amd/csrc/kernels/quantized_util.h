@@ -2,7 +2,7 @@
 // MIN_COMBINED quint8 mapping, the qint32 unit, and every float <-> quint8 /
 // qint32 conversion. This is their one definition: the CPU kernels
 // (kernels/cpu_quantized.cc) and the device code (kernels/hip/gemm_i8.hip,
-// kernels/hip/quantized.hip) both call it, so the two sides run the same IEEE
+// gemm_i8_fused.hip, quantized.hip) both call it, so the two sides run the same IEEE
 // operations in the same order and precision (f32 for the quint8 paths, f64
 // for the qint32 paths). A function in which a multiply feeds an add or a
 // subtract turns contraction off in its own body: a pragma in the including
@@ -74,11 +74,55 @@ STF_QHD uint8_t QuantizeU8(float x, float mn, float scale) {
   return (uint8_t)v;
 }
 
+// QuantizeV2's mx <= mn rule and its scale: *mx becomes the upper end in
+// use, the result is 255 / (*mx - mn).
+STF_QHD float QuantizeV2Scale(float mn, float* mx) {
+  if (*mx <= mn) *mx = mn + 1e-6f;
+  return 255.f / (*mx - mn);
+}
+
 // The quint8 that QuantizeV2 assigns to the scalar x under [mn, mx],
 // including its mx <= mn rule.
 STF_QHD uint8_t QuantizeScalarU8(float x, float mn, float mx) {
-  if (mx <= mn) mx = mn + 1e-6f;
-  return QuantizeU8(x, mn, 255.f / (mx - mn));
+  float scale = QuantizeV2Scale(mn, &mx);
+  return QuantizeU8(x, mn, scale);
+}
+
+// The fused conv / matmul epilogue (QuantizedConv2DWithBiasAndRequantize,
+// QuantizedMatMulWithBiasAndRequantize): the int32 accumulator in units of
+// m = step_input * step_filter, plus the float bias, through the activation,
+// to the quint8 of the requested range. All f32: two roundings in front of
+// the activation (no fma), one rounding to 8 bit, no divide per element. The
+// per-element result is QuantizeScalarU8(v, mn, mx) with the scale, which
+// does not depend on v, computed once.
+enum QuantActivation { kQuantActNone = 0, kQuantActRelu = 1,
+                       kQuantActRelu6 = 2 };
+
+struct QuantFusedScale {
+  float m;        // float value of one accumulator unit
+  float mn, mx;   // the output range: requested, after the mx <= mn rule
+  float scale;    // 255 / (mx - mn)
+};
+
+STF_QHD QuantFusedScale MakeQuantFusedScale(float min_a, float max_a,
+                                            float min_b, float max_b,
+                                            float req_min, float req_max) {
+  QuantFusedScale s;
+  s.m = QuantStep(min_a, max_a) * QuantStep(min_b, max_b);
+  s.mn = req_min;
+  s.mx = req_max;
+  s.scale = QuantizeV2Scale(s.mn, &s.mx);
+  return s;
+}
+
+template <int ACT>
+STF_QHD uint8_t QuantFusedU8(int32_t acc, float bias,
+                             const QuantFusedScale& s) {
+  STF_FP_CONTRACT_OFF
+  float v = (float)acc * s.m + bias;
+  if (ACT != kQuantActNone) v = 0.f < v ? v : 0.f;
+  if (ACT == kQuantActRelu6) v = v < 6.f ? v : 6.f;
+  return QuantizeU8(v, s.mn, s.scale);
 }
 
 // Dequantize of the quint8 q with step = QuantStep(mn, mx): two roundings.

@@ -774,6 +774,7 @@ def _conv_out_dim(in_dim, k, stride, padding):
 
 
 # The quantized ops return (tensor, min, max): the two ranges are scalars.
+@RegisterShape('QuantizedConv2DWithBiasAndRequantize')
 @RegisterShape('QuantizedConv2D')
 def _quantized_conv2d_shape(op):
     x, w = op.inputs[0]._shape, op.inputs[1]._shape
@@ -789,6 +790,7 @@ def _quantized_conv2d_shape(op):
              _conv_out_dim(wd, s, strides[2], padding), k), (), ()]
 
 
+@RegisterShape('QuantizedMatMulWithBiasAndRequantize')
 @RegisterShape('QuantizedMatMul')
 def _quantized_matmul_shape(op):
     a, b = op.inputs[0]._shape, op.inputs[1]._shape

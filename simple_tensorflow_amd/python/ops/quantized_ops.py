@@ -42,6 +42,44 @@ def quantized_conv2d(input, filter, min_input, max_input,  # noqa: A002
                     padding=padding, name=name)
 
 
+def quantized_conv2d_with_bias_and_requantize(
+        input, filter, bias, min_input, max_input,  # noqa: A002
+        min_filter, max_filter, requested_output_min, requested_output_max,
+        strides, padding, activation='None', name=None):
+    """quantized_conv2d, a float bias [cout], activation ('None', 'Relu' or
+    'Relu6') and the quantization to [requested_output_min,
+    requested_output_max] in one op -> (quint8 output, min_output,
+    max_output): out = quantize(activation(float(acc) * step_input *
+    step_filter + bias)), all in f32."""
+    return apply_op('QuantizedConv2DWithBiasAndRequantize', input, filter,
+                    convert_to_tensor(bias, dtype=dtypes.float32),
+                    convert_to_tensor(min_input),
+                    convert_to_tensor(max_input),
+                    convert_to_tensor(min_filter),
+                    convert_to_tensor(max_filter),
+                    convert_to_tensor(requested_output_min),
+                    convert_to_tensor(requested_output_max),
+                    strides=list(strides), padding=padding,
+                    activation=activation, name=name)
+
+
+def quantized_matmul_with_bias_and_requantize(
+        a, b, bias, min_a, max_a, min_b, max_b, requested_output_min,
+        requested_output_max, transpose_a=False, transpose_b=False,
+        activation='None', name=None):
+    """quantized_matmul with a float bias [N], activation and the
+    quantization to the requested range in one op -> (quint8 out, min_out,
+    max_out); see quantized_conv2d_with_bias_and_requantize."""
+    return apply_op('QuantizedMatMulWithBiasAndRequantize', a, b,
+                    convert_to_tensor(bias, dtype=dtypes.float32),
+                    convert_to_tensor(min_a), convert_to_tensor(max_a),
+                    convert_to_tensor(min_b), convert_to_tensor(max_b),
+                    convert_to_tensor(requested_output_min),
+                    convert_to_tensor(requested_output_max),
+                    transpose_a=transpose_a, transpose_b=transpose_b,
+                    activation=activation, name=name)
+
+
 def quantized_relu(features, min_features, max_features, name=None):
     return apply_op('QuantizedRelu', features,
                     convert_to_tensor(min_features),
@@ -122,7 +160,8 @@ def quantized_reshape(tensor, shape, input_min, input_max, name=None):
 
 
 for _op in ('QuantizeV2', 'Dequantize', 'QuantizedMatMul', 'QuantizedRelu',
-            'QuantizedConv2D',
+            'QuantizedConv2D', 'QuantizedConv2DWithBiasAndRequantize',
+            'QuantizedMatMulWithBiasAndRequantize',
             'QuantizeDownAndShrinkRange', 'RequantizationRange',
             'Requantize', 'QuantizedBiasAdd', 'QuantizedMaxPool',
             'QuantizedAvgPool', 'QuantizedRelu6', 'QuantizedConcat',

@@ -182,8 +182,53 @@ _REWRITES = {
 }
 
 
+_FUSED = {'Conv2D': 'QuantizedConv2DWithBiasAndRequantize',
+          'MatMul': 'QuantizedMatMulWithBiasAndRequantize'}
+
+
+def _match_epilogues(nodes, protected):
+    """Conv2D or MatMul -> BiasAdd [-> Relu or Relu6] chains that one fused
+    node can express: {name of the last node: (first node, BiasAdd node,
+    activation)} and the names of the nodes the fused one absorbs."""
+    readers = {}
+    for n in nodes:
+        for i in n['input']:
+            readers.setdefault(graph_util._base_name(i), []).append(n)
+
+    def plain(n, ops, ok):
+        return n['op'] in ops and _is_f32(n) and ok(n) and \
+            not any(i.startswith('^') for i in n['input'])
+
+    def only_reader(n):
+        """The node that alone reads n, through its first input."""
+        r = readers.get(n['name'], [])
+        if n['name'] in protected or len(r) != 1 or \
+                r[0]['input'][0] not in (n['name'], n['name'] + ':0'):
+            return None
+        return r[0]
+
+    fused, absorbed = {}, set()
+    for n in nodes:
+        if n['op'] not in _FUSED or \
+                not plain(n, _FUSED, _REWRITES[n['op']][3]):
+            continue
+        bias = only_reader(n)
+        # a BiasAdd that several nodes read keeps its own rewrite
+        if bias is None or not plain(bias, ('BiasAdd',), _nhwc) or \
+                len(readers.get(bias['name'], [])) > 1:
+            continue
+        last, activation = bias, 'None'
+        act = only_reader(bias)
+        if act is not None and plain(act, ('Relu', 'Relu6'), lambda a: True):
+            last, activation = act, act['op']
+            absorbed.add(bias['name'])
+        absorbed.add(n['name'])
+        fused[last['name']] = (n, bias, activation)
+    return fused, absorbed
+
+
 def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
-                   fallback_max=None):
+                   fallback_max=None, fuse_epilogue=False):
     """Rewrites float32 Conv2D, MatMul, BiasAdd, Relu, Relu6, MaxPool,
     AvgPool, Reshape, ConcatV2 and Concat (NHWC) to their quantized ops.
 
@@ -201,13 +246,29 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
     the uint8 tensor and its two range scalars directly.
 
     With fallback_min and fallback_max every RequantizationRange is replaced
-    by the two constants, which leaves no reduction behind the input."""
+    by the two constants, which leaves no reduction behind the input.
+
+    With fuse_epilogue (it needs the fallback pair: a measured range is a
+    global reduction and cannot be fused) a Conv2D or MatMul whose only
+    reader is a BiasAdd, itself read by at most one node, becomes one
+    QuantizedConv2D/MatMulWithBiasAndRequantize with the fallback pair as
+    its requested range; a Relu or Relu6 that alone reads the BiasAdd goes
+    into it as the activation. No absorbed node may be in inputs or outputs
+    or have a control input. The bias stays the float tensor it was. The
+    fused node is followed by a Dequantize with the last matched node's
+    name, which the second pass treats like any other."""
     if (fallback_min is None) != (fallback_max is None):
         raise ValueError('quantize_nodes needs both fallback_min and '
                          'fallback_max, or neither')
+    if fuse_epilogue and fallback_min is None:
+        raise ValueError('quantize_nodes(fuse_epilogue) needs fallback_min '
+                         'and fallback_max: a fused node cannot measure its '
+                         'output range')
     nodes = graph_util._as_nodes(graph_def)
     by_name = {n['name']: n for n in nodes}
     protected = set(inputs) | set(outputs)
+    fused, absorbed = _match_epilogues(nodes, protected) if fuse_epilogue \
+        else ({}, set())
 
     out = []
     const_done = set()
@@ -251,8 +312,35 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
             return [name + '/quint8_const', name + '/min', name + '/max']
         return [name + ':0', name + ':1', name + ':2']
 
+    def fallback_range(name):
+        """Emits the two constants of name; returns their names."""
+        out.append(_make_const(name + '/fallback_min',
+                               np.array(float(fallback_min), np.float32),
+                               _F32))
+        out.append(_make_const(name + '/fallback_max',
+                               np.array(float(fallback_max), np.float32),
+                               _F32))
+        return [name + '/fallback_min', name + '/fallback_max']
+
     # ---- first pass ----
     for n in nodes:
+        if n['name'] in absorbed:
+            continue
+        if n['name'] in fused:
+            first, bias, activation = fused[n['name']]
+            name, dev = n['name'], first.get('device', '')
+            ts = [triple(quantized_input(first['name'], k, first['input'][k]))
+                  for k in (0, 1)]
+            attr = {k: first['attr'][k] for k in _REWRITES[first['op']][4]
+                    if k in first['attr']}
+            attr['activation'] = ('s', activation.encode())
+            out.append(_node(name + '/eightbit', _FUSED[first['op']],
+                             [ts[0][0], ts[1][0], bias['input'][1]] +
+                             ts[0][1:] + ts[1][1:] + fallback_range(name),
+                             attr, dev))
+            out.append(_dequantize(name, name + '/eightbit', dev))
+            dequantized[name] = name + '/eightbit'
+            continue
         rw = _REWRITES.get(n['op'])
         if rw is None or not _is_f32(n) or not rw[3](n) or \
                 any(i.startswith('^') for i in n['input']):
@@ -286,13 +374,7 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
                                  {'Tinput': ('type', _I32)}, dev))
                 rng = [name + '/requant_range:0', name + '/requant_range:1']
             else:
-                out.append(_make_const(
-                    name + '/fallback_min',
-                    np.array(float(fallback_min), np.float32), _F32))
-                out.append(_make_const(
-                    name + '/fallback_max',
-                    np.array(float(fallback_max), np.float32), _F32))
-                rng = [name + '/fallback_min', name + '/fallback_max']
+                rng = fallback_range(name)
             out.append(_node(name + '/requantize', 'Requantize',
                              [last + ':0', last + ':1', last + ':2'] + rng,
                              {'Tinput': ('type', _I32),

@@ -106,7 +106,9 @@ def quantize_nodes(gd, inputs, outputs, params):
     return quantize_graph_lib.quantize_nodes(
         gd, inputs, outputs,
         fallback_min=_one(params, 'fallback_min', float),
-        fallback_max=_one(params, 'fallback_max', float))
+        fallback_max=_one(params, 'fallback_max', float),
+        fuse_epilogue=_one(params, 'fuse_epilogue',
+                           lambda v: v.lower() in ('1', 'true'), False))
 
 
 TRANSFORMS = {

@@ -24,6 +24,17 @@ filter, with the bf16 Conv2D beside them for orientation; and the same pair
 for a MatMul at (256*14*14, 256, 2304). The chain, the fused op and the bf16
 op take turns inside each of five rounds.
 
+With --fused-sum it times the closing conv of a ResNet stage-2 bottleneck
+block with its residual sum, (32,56,56,64) * 1x1x64x256 plus a
+(32,56,56,256) shortcut, Relu, in three forms: what quantize_nodes(
+fuse_epilogue=True) makes of Conv2D -> BiasAdd -> Add -> Relu without
+fuse_sum (the fused conv, two Dequantize, the f32 Add, the
+Reshape/Min/Max/QuantizeV2 group and QuantizedRelu), the plain fused conv
+alone, and the one QuantizedConv2DWithBiasSumAndRequantize. --tree DIR loads
+the package from another checkout, so that the chain can be timed on a build
+of the parent commit in a process of its own; a package without the sum op
+times the first two forms only.
+
 Needs a GPU; run it under a time limit:
   timeout 600 python scripts/quantized_inference_probe.py
 """
@@ -34,9 +45,13 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+# --tree DIR: the checkout whose package is loaded, this one by default
+_TREE = sys.argv[sys.argv.index('--tree') + 1] if '--tree' in sys.argv else \
+    os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _TREE)
 
 import simple_tensorflow_amd as tf  # noqa: E402
+from simple_tensorflow_amd.python.framework.ops import apply_op  # noqa: E402
 from simple_tensorflow_amd.python.ops import quantized_ops as q  # noqa: E402
 
 SHAPE = (32, 56, 56, 64)
@@ -222,6 +237,68 @@ def _fused_main(sess, args):
                  '%.1f' % np.median(us[2]) if bf16 else '-'), flush=True)
 
 
+# ---------------------------------------------------------------------------
+# --fused-sum: the closing conv of a bottleneck block with its residual sum
+# ---------------------------------------------------------------------------
+SUM_FILTER = (1, 1, 64, 256)
+HAS_SUM = hasattr(q, 'quantized_conv2d_with_bias_sum_and_requantize')
+
+
+def _sum_makes():
+    """[(name, make)]: the unfused chain, the plain fused conv, the sum op."""
+    short_shape = SHAPE[:3] + (SUM_FILTER[3],)
+    with tf.device('/gpu:0'):
+        x = tf.Variable(tf.random_uniform(SHAPE, -1.0, 1.0))
+        w = tf.Variable(tf.random_uniform(SUM_FILTER, -1.0, 1.0))
+        b = tf.Variable(tf.random_uniform((SUM_FILTER[3],), -1.0, 1.0))
+        sc = tf.Variable(tf.random_uniform(short_shape, 0.0, 4.0))
+        x8, w8 = [q.quantize_v2(t, -1.0, 1.0) for t in (x, w)]
+        s8 = q.quantize_v2(sc, REQ[0], REQ[1])
+
+    def conv(activation):
+        return q.quantized_conv2d_with_bias_and_requantize(
+            x8[0], w8[0], b, x8[1], x8[2], w8[1], w8[2], REQ[0], REQ[1],
+            [1, 1, 1, 1], 'VALID', activation=activation)
+
+    def chain():
+        y = tf.add(q.dequantize(*conv('None')), q.dequantize(*s8))
+        flat = tf.reshape(y, [-1])
+        # the wrapper takes constants only; the range is measured here
+        y8 = apply_op('QuantizeV2', y, tf.reduce_min(flat, [0]),
+                      tf.reduce_max(flat, [0]), mode='MIN_COMBINED')
+        return q.quantized_relu(*y8)[0]
+
+    def fused_sum():
+        return q.quantized_conv2d_with_bias_sum_and_requantize(
+            x8[0], w8[0], b, s8[0], x8[1], x8[2], w8[1], w8[2], s8[1], s8[2],
+            REQ[0], REQ[1], [1, 1, 1, 1], 'VALID', activation='Relu')[0]
+
+    makes = [('chain', chain), ('fused conv', lambda: conv('Relu')[0])]
+    return makes + ([('fused sum', fused_sum)] if HAS_SUM else [])
+
+
+def _fused_sum_main(sess, args):
+    makes = _sum_makes()
+    sess.run(tf.global_variables_initializer())
+    if args.profile:  # for a kernel trace: a few runs of each, no timing
+        for _, make in makes:
+            with tf.device('/gpu:0'):
+                op = _chained(make, 4)
+            for _ in range(3):
+                sess.run(op)
+            sess.sync()
+        return
+    t = _alternating(sess, [m for _, m in makes], args.lo, args.hi,
+                     args.warmup, args.iters)
+    print('| tree | form | us, median (rounds) |')
+    print('|---|---|---|')
+    for (name, _), r in zip(makes, t):
+        us = [v * 1e6 for v in r]
+        print('| %s | %s | %.1f (%s) |'
+              % (_TREE, name, np.median(us),
+                 ', '.join('%.1f' % v for v in us)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--lo', type=int, default=4)
@@ -231,8 +308,15 @@ def main():
     ap.add_argument('--fused', action='store_true',
                     help='time one quantized layer as the chain of five ops '
                          'against the fused op, and nothing else')
+    ap.add_argument('--fused-sum', action='store_true',
+                    help='time the conv + residual sum + Relu of a '
+                         'bottleneck block as the unfused chain, the plain '
+                         'fused conv and the fused-sum op, and nothing else')
+    ap.add_argument('--tree', default=_TREE,
+                    help='the checkout whose package is loaded (a build of '
+                         'the parent commit as the yardstick)')
     ap.add_argument('--profile', action='store_true',
-                    help='with --fused: run the chain and the fused op a few '
+                    help='with --fused or --fused-sum: run each form a few '
                          'times and exit, for rocprofv3 --kernel-trace '
                          '--stats in a run of its own')
     args = ap.parse_args()
@@ -241,6 +325,8 @@ def main():
     assert sess.num_gpus() > 0, 'the probe needs a GPU'
     if args.fused:
         return _fused_main(sess, args)
+    if args.fused_sum:
+        return _fused_sum_main(sess, args)
     cases = _cases()
     sess.run(tf.global_variables_initializer())
 

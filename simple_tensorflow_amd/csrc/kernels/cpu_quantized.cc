@@ -98,27 +98,38 @@ void QuantMatMulLoop(const uint8_t* ap, const uint8_t* bp, int64_t M,
     }
 }
 
+// The quint8 summand of the fused conv with a residual sum: one value per
+// output element, its range's start and step. q is null without one.
+struct QuantSummand {
+  const uint8_t* q = nullptr;
+  float mn = 0, step = 0;
+};
+
 // The fused epilogue as an accumulation sink (kernels/quantized_util.h).
 template <int ACT>
 struct QuantFusedSink {
   uint8_t* out;
   const float* bias;
   QuantFusedScale sc;
+  QuantSummand sum;
   void operator()(int64_t i, int64_t c, int32_t acc) const {
-    out[i] = QuantFusedU8<ACT>(acc, bias[c], sc);
+    out[i] = sum.q ? QuantFusedSumU8<ACT>(acc, bias[c], sum.q[i], sum.mn,
+                                          sum.step, sc)
+                   : QuantFusedU8<ACT>(acc, bias[c], sc);
   }
 };
 
 // run(sink) with the sink of the activation act.
 template <class Run>
 void WithQuantFusedSink(int act, uint8_t* out, const float* bias,
-                        const QuantFusedScale& sc, Run run) {
+                        const QuantFusedScale& sc, const QuantSummand& sum,
+                        Run run) {
   if (act == kQuantActRelu6)
-    run(QuantFusedSink<kQuantActRelu6>{out, bias, sc});
+    run(QuantFusedSink<kQuantActRelu6>{out, bias, sc, sum});
   else if (act == kQuantActRelu)
-    run(QuantFusedSink<kQuantActRelu>{out, bias, sc});
+    run(QuantFusedSink<kQuantActRelu>{out, bias, sc, sum});
   else
-    run(QuantFusedSink<kQuantActNone>{out, bias, sc});
+    run(QuantFusedSink<kQuantActNone>{out, bias, sc, sum});
 }
 
 // out_int32 = sum (a_q - a_zero) * (b_q - b_zero) in float-equivalent units:
@@ -163,7 +174,8 @@ class QuantizedMatMulOp : public OpKernel {
       QuantFusedScale sc = MakeQuantFusedScale(
           min_a, max_a, min_b, max_b, RangeIn(ctx, 7), RangeIn(ctx, 8));
       WithQuantFusedSink(act_, out->flat<uint8_t>(),
-                         ctx->input(2).flat<float>(), sc, [&](auto sink) {
+                         ctx->input(2).flat<float>(), sc, QuantSummand{},
+                         [&](auto sink) {
                            QuantMatMulLoop(ap, bp, M, N, K, ta_, tb_, za, zb,
                                            sink);
                          });
@@ -200,6 +212,9 @@ REGISTER_KERNEL_BUILDER(
 // QuantizedConv2DWithBiasAndRequantize (fused) sends the same sums through
 // the fused epilogue: inputs input, filter, bias, the four ranges, the
 // requested output range; quint8 output.
+// QuantizedConv2DWithBiasSumAndRequantize (sum) adds a quint8 summand of the
+// output's shape in front of the activation: inputs input, filter, bias,
+// summand, the four ranges, the summand's range, the requested output range.
 template <class Sink>
 void QuantConvLoop(const ConvGeom& g, const uint8_t* xp, const uint8_t* wp,
                    int32_t zx, int32_t zf, Sink sink) {
@@ -230,26 +245,32 @@ void QuantConvLoop(const ConvGeom& g, const uint8_t* xp, const uint8_t* wp,
 
 class QuantizedConv2DOp : public OpKernel {
  public:
-  QuantizedConv2DOp(OpKernelConstruction* c, bool fused)
-      : OpKernel(c), fused_(fused), attrs_(c) {
+  QuantizedConv2DOp(OpKernelConstruction* c, bool fused, bool sum)
+      : OpKernel(c), fused_(fused), sum_(sum), attrs_(c) {
     if (fused_) act_ = QuantFusedActivation(c);
   }
   explicit QuantizedConv2DOp(OpKernelConstruction* c)
-      : QuantizedConv2DOp(c, false) {}
+      : QuantizedConv2DOp(c, false, false) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& w = ctx->input(1);
     ConvGeom g;
     OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g));
+    TensorShape out_shape({g.N, g.P, g.Q, g.K});
     if (fused_)
       OP_REQUIRES_OK(ctx, QuantFusedBiasDims(attrs_.op,
                                              ctx->input(2).shape(), g.K));
-    int r = fused_ ? 3 : 2;  // the first range input
+    if (sum_)
+      OP_REQUIRES_OK(ctx, QuantFusedSummandDims(
+                              attrs_.op, ctx->input(3).shape(), out_shape));
+    // the first range input; the requested range follows the input ranges
+    int r = 2 + (fused_ ? 1 : 0) + (sum_ ? 1 : 0);
+    int req = r + (sum_ ? 6 : 4);
     float min_x = RangeIn(ctx, r);
     float max_x = RangeIn(ctx, r + 1);
     float min_w = RangeIn(ctx, r + 2);
     float max_w = RangeIn(ctx, r + 3);
-    Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.K}));
+    Tensor* out = ctx->allocate_output(0, out_shape);
     const uint8_t* xp = x.flat<uint8_t>();
     const uint8_t* wp = w.flat<uint8_t>();
     float sx = QuantStep(min_x, max_x);
@@ -258,9 +279,15 @@ class QuantizedConv2DOp : public OpKernel {
     int32_t zf = QuantZeroPoint(min_w, max_w);
     if (fused_) {
       QuantFusedScale sc = MakeQuantFusedScale(
-          min_x, max_x, min_w, max_w, RangeIn(ctx, 7), RangeIn(ctx, 8));
+          min_x, max_x, min_w, max_w, RangeIn(ctx, req), RangeIn(ctx, req + 1));
+      QuantSummand sum;
+      if (sum_) {
+        sum.q = ctx->input(3).flat<uint8_t>();
+        sum.mn = RangeIn(ctx, r + 4);
+        sum.step = QuantStep(sum.mn, RangeIn(ctx, r + 5));
+      }
       WithQuantFusedSink(
-          act_, out->flat<uint8_t>(), ctx->input(2).flat<float>(), sc,
+          act_, out->flat<uint8_t>(), ctx->input(2).flat<float>(), sc, sum,
           [&](auto sink) { QuantConvLoop(g, xp, wp, zx, zf, sink); });
       RangeOut(ctx, 1, sc.mn, sc.mx);
       return;
@@ -272,20 +299,28 @@ class QuantizedConv2DOp : public OpKernel {
   }
 
  private:
-  bool fused_;
+  bool fused_, sum_;
   ConvAttrs attrs_;
   int act_ = 0;
 };
 class QuantizedConv2DFusedOp : public QuantizedConv2DOp {
  public:
   explicit QuantizedConv2DFusedOp(OpKernelConstruction* c)
-      : QuantizedConv2DOp(c, true) {}
+      : QuantizedConv2DOp(c, true, false) {}
+};
+class QuantizedConv2DFusedSumOp : public QuantizedConv2DOp {
+ public:
+  explicit QuantizedConv2DFusedSumOp(OpKernelConstruction* c)
+      : QuantizedConv2DOp(c, true, true) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_CPU),
                         QuantizedConv2DOp);
 REGISTER_KERNEL_BUILDER(
     Name("QuantizedConv2DWithBiasAndRequantize").Device(DEVICE_CPU),
     QuantizedConv2DFusedOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedConv2DWithBiasSumAndRequantize").Device(DEVICE_CPU),
+    QuantizedConv2DFusedSumOp);
 
 class QuantizedReluOp : public OpKernel {
  public:

@@ -1,6 +1,7 @@
 // GPU OpKernels: the quantized family (QuantizeV2, Dequantize,
 // QuantizedMatMul, QuantizedConv2D, their fused forms
-// Quantized{MatMul,Conv2D}WithBiasAndRequantize, QuantizedRelu,
+// Quantized{MatMul,Conv2D}WithBiasAndRequantize,
+// QuantizedConv2DWithBiasSumAndRequantize, QuantizedRelu,
 // RequantizationRange,
 // QuantizeDownAndShrinkRange, Requantize, QuantizedBiasAdd,
 // QuantizedMaxPool, QuantizedAvgPool, QuantizedRelu6, QuantizedConcat) on
@@ -152,16 +153,18 @@ REGISTER_KERNEL_BUILDER(
     Name("QuantizedMatMulWithBiasAndRequantize").Device(DEVICE_GPU),
     GpuQuantizedMatMulFusedOp);
 
-// QuantizedConv2D, and with fused QuantizedConv2DWithBiasAndRequantize
-// (inputs: input, filter, bias, the four ranges, the requested range).
+// QuantizedConv2D, with fused QuantizedConv2DWithBiasAndRequantize (inputs:
+// input, filter, bias, the four ranges, the requested range), and with sum
+// QuantizedConv2DWithBiasSumAndRequantize (a quint8 summand of the output's
+// shape behind the bias, its range behind the four ranges).
 class GpuQuantizedConv2DOp : public OpKernel {
  public:
-  GpuQuantizedConv2DOp(OpKernelConstruction* c, bool fused)
-      : OpKernel(c), fused_(fused), attrs_(c) {
+  GpuQuantizedConv2DOp(OpKernelConstruction* c, bool fused, bool sum)
+      : OpKernel(c), fused_(fused), sum_(sum), attrs_(c) {
     if (fused_) act_ = QuantFusedActivation(c);
   }
   explicit GpuQuantizedConv2DOp(OpKernelConstruction* c)
-      : GpuQuantizedConv2DOp(c, false) {}
+      : GpuQuantizedConv2DOp(c, false, false) {}
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& w = ctx->input(1);
@@ -169,12 +172,17 @@ class GpuQuantizedConv2DOp : public OpKernel {
     ConvGeom cg;
     StfConvGeom g;
     OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &cg, &g));
+    TensorShape out_shape({cg.N, cg.P, cg.Q, cg.K});
     if (fused_)
       OP_REQUIRES_OK(ctx, QuantFusedBiasDims(attrs_.op,
                                              ctx->input(2).shape(), cg.K));
-    int r = fused_ ? 3 : 2;  // the first range input
-    Tensor* y = ctx->allocate_output(0,
-                                     TensorShape({cg.N, cg.P, cg.Q, cg.K}));
+    if (sum_)
+      OP_REQUIRES_OK(ctx, QuantFusedSummandDims(
+                              attrs_.op, ctx->input(3).shape(), out_shape));
+    // the first range input; the requested range follows the input ranges
+    int r = 2 + (fused_ ? 1 : 0) + (sum_ ? 1 : 0);
+    int req = r + (sum_ ? 6 : 4);
+    Tensor* y = ctx->allocate_output(0, out_shape);
     float* omn = ScalarOut(ctx, 1);
     float* omx = ScalarOut(ctx, 2);
     int64_t rsc = cg.RSC();
@@ -192,13 +200,25 @@ class GpuQuantizedConv2DOp : public OpKernel {
       OP_HIP_OK(ctx, stf_im2col_i8(x.raw_data(), col.raw_data(), &g, kp, s));
       ap = col.raw_data();
     }
+    if (sum_) {
+      OP_HIP_OK(ctx, stf_conv2d_i8_fused_sum(
+                         ap, implicit ? 1 : 0, wp.raw_data(),
+                         (const int32_t*)wsums.raw_data(), F32(ctx->input(2)),
+                         (const uint8_t*)ctx->input(3).raw_data(),
+                         F32(ctx->input(r)), F32(ctx->input(r + 1)),
+                         F32(ctx->input(r + 2)), F32(ctx->input(r + 3)),
+                         F32(ctx->input(r + 4)), F32(ctx->input(r + 5)),
+                         F32(ctx->input(req)), F32(ctx->input(req + 1)), act_,
+                         (uint8_t*)y->raw_data(), omn, omx, &g, s));
+      return;
+    }
     if (fused_) {
       OP_HIP_OK(ctx, stf_conv2d_i8_fused(
                          ap, implicit ? 1 : 0, wp.raw_data(),
                          (const int32_t*)wsums.raw_data(), F32(ctx->input(2)),
                          F32(ctx->input(r)), F32(ctx->input(r + 1)),
                          F32(ctx->input(r + 2)), F32(ctx->input(r + 3)),
-                         F32(ctx->input(7)), F32(ctx->input(8)), act_,
+                         F32(ctx->input(req)), F32(ctx->input(req + 1)), act_,
                          (uint8_t*)y->raw_data(), omn, omx, &g, s));
       return;
     }
@@ -210,20 +230,28 @@ class GpuQuantizedConv2DOp : public OpKernel {
   }
 
  private:
-  bool fused_;
+  bool fused_, sum_;
   ConvAttrs attrs_;
   int act_ = 0;
 };
 class GpuQuantizedConv2DFusedOp : public GpuQuantizedConv2DOp {
  public:
   explicit GpuQuantizedConv2DFusedOp(OpKernelConstruction* c)
-      : GpuQuantizedConv2DOp(c, true) {}
+      : GpuQuantizedConv2DOp(c, true, false) {}
+};
+class GpuQuantizedConv2DFusedSumOp : public GpuQuantizedConv2DOp {
+ public:
+  explicit GpuQuantizedConv2DFusedSumOp(OpKernelConstruction* c)
+      : GpuQuantizedConv2DOp(c, true, true) {}
 };
 REGISTER_KERNEL_BUILDER(Name("QuantizedConv2D").Device(DEVICE_GPU),
                         GpuQuantizedConv2DOp);
 REGISTER_KERNEL_BUILDER(
     Name("QuantizedConv2DWithBiasAndRequantize").Device(DEVICE_GPU),
     GpuQuantizedConv2DFusedOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedConv2DWithBiasSumAndRequantize").Device(DEVICE_GPU),
+    GpuQuantizedConv2DFusedSumOp);
 
 // QuantizedRelu and QuantizedRelu6: two entry points of one signature.
 using QuantizedClampFn = hipError_t (*)(const uint8_t*, const float*,

@@ -190,6 +190,17 @@ hipError_t stf_conv2d_i8_fused(const void* x_or_col, int implicit,
                                const float* req_max, int activation,
                                uint8_t* y, float* min_out, float* max_out,
                                const StfConvGeom* g, hipStream_t stream);
+// stf_conv2d_i8_fused with a residual sum in front of the activation
+// (stf::QuantFusedSumU8): summand is a device quint8 tensor of y's shape
+// [n*p*q][cout], 16-byte aligned, under the range of the device f32 scalars
+// min_s, max_s.
+hipError_t stf_conv2d_i8_fused_sum(
+    const void* x_or_col, int implicit, const void* wp, const int32_t* wsums,
+    const float* bias, const uint8_t* summand, const float* min_x,
+    const float* max_x, const float* min_w, const float* max_w,
+    const float* min_s, const float* max_s, const float* req_min,
+    const float* req_max, int activation, uint8_t* y, float* min_out,
+    float* max_out, const StfConvGeom* g, hipStream_t stream);
 
 // ---- quantized.hip ----
 // Bit-equal to the CPU kernels (kernels/cpu_quantized.cc). Ranges are device

@@ -48,6 +48,18 @@ inline Status QuantFusedBiasDims(const std::string& op,
   return Status::OK();
 }
 
+// The quint8 summand of QuantizedConv2DWithBiasSumAndRequantize: exactly the
+// output's shape, no broadcasting.
+inline Status QuantFusedSummandDims(const std::string& op,
+                                    const TensorShape& summand,
+                                    const TensorShape& out) {
+  if (summand != out)
+    return errors::InvalidArgument(op, ": summand must have the output's "
+                                   "shape ", out.DebugString(), ", got ",
+                                   summand.DebugString());
+  return Status::OK();
+}
+
 // The activation attribute of the fused ops -> QuantActivation
 // (kernels/quantized_util.h). Anything else fails the kernel's construction.
 inline QuantActivation QuantFusedActivation(OpKernelConstruction* c) {

@@ -131,6 +131,23 @@ STF_QHD float DequantizeU8(uint32_t q, float mn, float step) {
   return mn + (float)q * step;
 }
 
+// QuantFusedU8 with a residual sum in front of the activation
+// (QuantizedConv2DWithBiasSumAndRequantize): the quint8 summand q_summand of
+// the range that starts at min_summand, step_s = QuantStep(min_summand,
+// max_summand), is dequantized and added to acc * m + bias. In this order:
+// two roundings, Dequantize's two, one for the sum.
+template <int ACT>
+STF_QHD uint8_t QuantFusedSumU8(int32_t acc, float bias, uint32_t q_summand,
+                                float min_summand, float step_s,
+                                const QuantFusedScale& s) {
+  STF_FP_CONTRACT_OFF
+  float v = (float)acc * s.m + bias;
+  v = v + DequantizeU8(q_summand, min_summand, step_s);
+  if (ACT != kQuantActNone) v = 0.f < v ? v : 0.f;
+  if (ACT == kQuantActRelu6) v = v < 6.f ? v : 6.f;
+  return QuantizeU8(v, s.mn, s.scale);
+}
+
 // Dequantize of the qint32 p with scale = QuantUnitI32(mn, mx): the int32
 // range maps onto [mn, mx].
 STF_QHD float DequantizeI32(int32_t p, double scale, float mn) {

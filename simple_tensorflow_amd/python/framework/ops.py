@@ -774,6 +774,7 @@ def _conv_out_dim(in_dim, k, stride, padding):
 
 
 # The quantized ops return (tensor, min, max): the two ranges are scalars.
+@RegisterShape('QuantizedConv2DWithBiasSumAndRequantize')
 @RegisterShape('QuantizedConv2DWithBiasAndRequantize')
 @RegisterShape('QuantizedConv2D')
 def _quantized_conv2d_shape(op):

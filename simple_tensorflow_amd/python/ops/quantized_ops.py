@@ -63,6 +63,30 @@ def quantized_conv2d_with_bias_and_requantize(
                     activation=activation, name=name)
 
 
+def quantized_conv2d_with_bias_sum_and_requantize(
+        input, filter, bias, summand, min_input, max_input,  # noqa: A002
+        min_filter, max_filter, min_summand, max_summand,
+        requested_output_min, requested_output_max, strides, padding,
+        activation='None', name=None):
+    """quantized_conv2d_with_bias_and_requantize with a residual sum in
+    front of the activation: summand is a quint8 tensor of exactly the
+    output's shape [N, P, Q, cout] (no broadcasting) under [min_summand,
+    max_summand]. out = quantize(activation(float(acc) * step_input *
+    step_filter + bias + dequantize(summand))), all in f32."""
+    return apply_op('QuantizedConv2DWithBiasSumAndRequantize', input, filter,
+                    convert_to_tensor(bias, dtype=dtypes.float32), summand,
+                    convert_to_tensor(min_input),
+                    convert_to_tensor(max_input),
+                    convert_to_tensor(min_filter),
+                    convert_to_tensor(max_filter),
+                    convert_to_tensor(min_summand),
+                    convert_to_tensor(max_summand),
+                    convert_to_tensor(requested_output_min),
+                    convert_to_tensor(requested_output_max),
+                    strides=list(strides), padding=padding,
+                    activation=activation, name=name)
+
+
 def quantized_matmul_with_bias_and_requantize(
         a, b, bias, min_a, max_a, min_b, max_b, requested_output_min,
         requested_output_max, transpose_a=False, transpose_b=False,
@@ -161,6 +185,7 @@ def quantized_reshape(tensor, shape, input_min, input_max, name=None):
 
 for _op in ('QuantizeV2', 'Dequantize', 'QuantizedMatMul', 'QuantizedRelu',
             'QuantizedConv2D', 'QuantizedConv2DWithBiasAndRequantize',
+            'QuantizedConv2DWithBiasSumAndRequantize',
             'QuantizedMatMulWithBiasAndRequantize',
             'QuantizeDownAndShrinkRange', 'RequantizationRange',
             'Requantize', 'QuantizedBiasAdd', 'QuantizedMaxPool',

@@ -186,10 +186,16 @@ _FUSED = {'Conv2D': 'QuantizedConv2DWithBiasAndRequantize',
           'MatMul': 'QuantizedMatMulWithBiasAndRequantize'}
 
 
-def _match_epilogues(nodes, protected):
+_FUSED_SUM = 'QuantizedConv2DWithBiasSumAndRequantize'
+
+
+def _match_epilogues(nodes, protected, fuse_sum=False):
     """Conv2D or MatMul -> BiasAdd [-> Relu or Relu6] chains that one fused
     node can express: {name of the last node: (first node, BiasAdd node,
-    activation)} and the names of the nodes the fused one absorbs."""
+    activation, summand)} and the names of the nodes the fused one absorbs.
+    summand is None, or with fuse_sum the other input of the f32 Add that
+    alone reads a Conv2D chain's BiasAdd: Conv2D -> BiasAdd -> Add [-> Relu
+    or Relu6] is one node then."""
     readers = {}
     for n in nodes:
         for i in n['input']:
@@ -199,15 +205,19 @@ def _match_epilogues(nodes, protected):
         return n['op'] in ops and _is_f32(n) and ok(n) and \
             not any(i.startswith('^') for i in n['input'])
 
-    def only_reader(n):
-        """The node that alone reads n, through its first input."""
+    def only_reader(n, any_input=False):
+        """The node that alone reads n, through its first input (through
+        one input, whichever, with any_input)."""
         r = readers.get(n['name'], [])
-        if n['name'] in protected or len(r) != 1 or \
-                r[0]['input'][0] not in (n['name'], n['name'] + ':0'):
+        if n['name'] in protected or len(r) != 1:
+            return None
+        reads = r[0]['input'] if any_input else r[0]['input'][:1]
+        if not any(i in (n['name'], n['name'] + ':0') for i in reads):
             return None
         return r[0]
 
     fused, absorbed = {}, set()
+    sums = {}  # Add name -> the chain that takes it: the last in node order
     for n in nodes:
         if n['op'] not in _FUSED or \
                 not plain(n, _FUSED, _REWRITES[n['op']][3]):
@@ -223,12 +233,27 @@ def _match_epilogues(nodes, protected):
             last, activation = act, act['op']
             absorbed.add(bias['name'])
         absorbed.add(n['name'])
-        fused[last['name']] = (n, bias, activation)
+        fused[last['name']] = (n, bias, activation, None)
+        add = only_reader(bias, any_input=True) \
+            if fuse_sum and n['op'] == 'Conv2D' else None
+        if add is not None and plain(add, ('Add',), lambda a: True) and \
+                add['name'] not in protected:
+            sums[add['name']] = (n, bias, add)
+    for n, bias, add in sums.values():
+        del fused[bias['name']]
+        absorbed.add(bias['name'])
+        last, activation = add, 'None'
+        act = only_reader(add)
+        if act is not None and plain(act, ('Relu', 'Relu6'), lambda a: True):
+            last, activation = act, act['op']
+            absorbed.add(add['name'])
+        k = 0 if graph_util._base_name(add['input'][1]) == bias['name'] else 1
+        fused[last['name']] = (n, bias, activation, add['input'][k])
     return fused, absorbed
 
 
 def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
-                   fallback_max=None, fuse_epilogue=False):
+                   fallback_max=None, fuse_epilogue=False, fuse_sum=False):
     """Rewrites float32 Conv2D, MatMul, BiasAdd, Relu, Relu6, MaxPool,
     AvgPool, Reshape, ConcatV2 and Concat (NHWC) to their quantized ops.
 
@@ -256,7 +281,21 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
     into it as the activation. No absorbed node may be in inputs or outputs
     or have a control input. The bias stays the float tensor it was. The
     fused node is followed by a Dequantize with the last matched node's
-    name, which the second pass treats like any other."""
+    name, which the second pass treats like any other.
+
+    With fuse_sum (it needs fuse_epilogue) a fusable Conv2D -> BiasAdd whose
+    only reader is a float32 Add, through either input, takes the Add in as
+    well: with a Relu or Relu6 that alone reads the Add it becomes one
+    QuantizedConv2DWithBiasSumAndRequantize, whose summand is the Add's
+    other input, quantized like any activation, so that the second pass
+    hands it the producer's quint8 tensor. The Add has no control input and
+    is in neither inputs nor outputs. When both inputs of the Add are such
+    chains (a projection shortcut) the one whose Conv2D comes later in node
+    order takes the sum and the other is an ordinary fused node without an
+    activation. The rewrite cannot see shapes and the op does not
+    broadcast: fuse_sum is the caller's statement that the matched Adds add
+    tensors of equal shape, as a residual block's do; the op's check at run
+    time (InvalidArgument) catches the rest."""
     if (fallback_min is None) != (fallback_max is None):
         raise ValueError('quantize_nodes needs both fallback_min and '
                          'fallback_max, or neither')
@@ -264,11 +303,13 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
         raise ValueError('quantize_nodes(fuse_epilogue) needs fallback_min '
                          'and fallback_max: a fused node cannot measure its '
                          'output range')
+    if fuse_sum and not fuse_epilogue:
+        raise ValueError('quantize_nodes(fuse_sum) needs fuse_epilogue')
     nodes = graph_util._as_nodes(graph_def)
     by_name = {n['name']: n for n in nodes}
     protected = set(inputs) | set(outputs)
-    fused, absorbed = _match_epilogues(nodes, protected) if fuse_epilogue \
-        else ({}, set())
+    fused, absorbed = _match_epilogues(nodes, protected, fuse_sum) \
+        if fuse_epilogue else ({}, set())
 
     out = []
     const_done = set()
@@ -327,17 +368,24 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
         if n['name'] in absorbed:
             continue
         if n['name'] in fused:
-            first, bias, activation = fused[n['name']]
+            first, bias, activation, summand = fused[n['name']]
             name, dev = n['name'], first.get('device', '')
-            ts = [triple(quantized_input(first['name'], k, first['input'][k]))
-                  for k in (0, 1)]
+            ins = [first['input'][0], first['input'][1]] + \
+                ([] if summand is None else [summand])
+            ts = [triple(quantized_input(first['name'], k, i))
+                  for k, i in enumerate(ins)]
             attr = {k: first['attr'][k] for k in _REWRITES[first['op']][4]
                     if k in first['attr']}
             attr['activation'] = ('s', activation.encode())
-            out.append(_node(name + '/eightbit', _FUSED[first['op']],
+            # the tensors with the float bias behind the filter, the ranges
+            # in the same order, the requested range
+            out.append(_node(name + '/eightbit',
+                             _FUSED[first['op']] if summand is None
+                             else _FUSED_SUM,
                              [ts[0][0], ts[1][0], bias['input'][1]] +
-                             ts[0][1:] + ts[1][1:] + fallback_range(name),
-                             attr, dev))
+                             [t[0] for t in ts[2:]] +
+                             [r for t in ts for r in t[1:]] +
+                             fallback_range(name), attr, dev))
             out.append(_dequantize(name, name + '/eightbit', dev))
             dequantized[name] = name + '/eightbit'
             continue

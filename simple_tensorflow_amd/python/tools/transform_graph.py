@@ -108,7 +108,9 @@ def quantize_nodes(gd, inputs, outputs, params):
         fallback_min=_one(params, 'fallback_min', float),
         fallback_max=_one(params, 'fallback_max', float),
         fuse_epilogue=_one(params, 'fuse_epilogue',
-                           lambda v: v.lower() in ('1', 'true'), False))
+                           lambda v: v.lower() in ('1', 'true'), False),
+        fuse_sum=_one(params, 'fuse_sum',
+                      lambda v: v.lower() in ('1', 'true'), False))
 
 
 TRANSFORMS = {

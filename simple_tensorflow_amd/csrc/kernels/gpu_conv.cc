@@ -280,9 +280,11 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
  public:
   explicit GpuConv2DBackpropFilterOp(OpKernelConstruction* c)
       : OpKernel(c), attrs_(c) {
-    // STF_NO_TALL_DW (A/B runs) keeps every dW on the split-K GEMM. Read per
-    // kernel, so a new graph sees a changed setting.
+    // STF_NO_TALL_DW and STF_NO_WIDE_DW (A/B runs) keep the shapes of that
+    // kernel on the split-K GEMM. Read per kernel, so a new graph sees a
+    // changed setting.
     tall_dw_ = getenv("STF_NO_TALL_DW") == nullptr;
+    wide_dw_ = getenv("STF_NO_WIDE_DW") == nullptr;
   }
   void Compute(OpKernelContext* ctx) override {
     hipStream_t s = GPU_STREAM(ctx);
@@ -331,11 +333,19 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
       // cout 64 with a short filter (ResNet's stem and stage-2 3x3): one
       // block holds all of dW and x and dy are streamed once, instead of
       // split-K over the im2col expansion.
+      // Other cout = 64*k shapes (ResNet's 3x3 of stages 3-5 and stride-2
+      // 1x1, Inception's long filters): dW tiled by channel and cout slices,
+      // x and dy still staged in NHWC order, no im2col expansion. What
+      // neither gate takes (cout 136, 16, M < 768, ...) stays on split-K.
       bool tall = tall_dw_ && stf_conv2d_dw_tall_ok(&si);
-      int sk = tall ? 0 : PickSplitK(gi.RSC(), g.K, g.M());
+      bool wide = !tall && wide_dw_ && stf_conv2d_dw_wide_ok(&si);
+      int sk = tall || wide ? 0 : PickSplitK(gi.RSC(), g.K, g.M());
       OP_HIP_OK(ctx, SplitKInto(ctx, gi.RSC() * g.K, [&](float* acc) {
         if (tall)
           return stf_conv2d_dw_tall(xdata, dy.raw_data(), acc, ZeroPage(),
+                                    &si, s);
+        if (wide)
+          return stf_conv2d_dw_wide(xdata, dy.raw_data(), acc, ZeroPage(),
                                     &si, s);
         return stf_conv2d_dw_splitk(xdata, dy.raw_data(), acc, ZeroPage(),
                                     &si, sk, s);
@@ -368,7 +378,7 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
 
  private:
   ConvAttrs attrs_;
-  bool tall_dw_;
+  bool tall_dw_, wide_dw_;
 };
 REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropFilter").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("filter_sizes"), GpuConv2DBackpropFilterOp);
 

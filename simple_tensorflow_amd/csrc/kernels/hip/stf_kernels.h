@@ -115,7 +115,8 @@ hipError_t stf_conv2d_dx_8ph(const void* dy, const void* wt, void* dx,
 // ---- conv_dw_tall.hip ----
 // Backprop-filter of a cout = 64 convolution with one block holding the whole
 // [r*s*c, 64] f32 output: adds into the zeroed dw_f32 with atomics, like
-// stf_conv2d_dw_splitk. The gate (stf_conv2d_dw_tall_ok): cout == 64,
+// stf_conv2d_dw_splitk. Shapes outside its gate go to stf_conv2d_dw_wide
+// (below) and only then to split-K. The gate (stf_conv2d_dw_tall_ok): cout == 64,
 // c % 8 == 0, r*s*c <= 576, n*p*q % 64 == 0, n*p*q >= 768, and three LDS
 // buffers of 16 * (roundup(r * (31*sw + s) * c/8, 256) + 256) bytes within
 // 160 KiB (and one image's h*w*c below 2^31).
@@ -128,6 +129,24 @@ hipError_t stf_conv2d_dw_tall(const void* x, const void* dy, void* dw_f32,
 // register of each lane (row = lane % 16, k = 8 * (lane / 16) + 0..7).
 hipError_t stf_conv2d_dw_tall_frag_probe(const void* tile_u16, void* out_u16,
                                          hipStream_t stream);
+
+// ---- conv_dw_wide.hip ----
+// Backprop-filter of a cout = 64*k convolution outside the tall gate, tiled
+// into (channel slice of CS) x (128 columns) pieces of dW, each summed over
+// 2-D patches of 32 output pixels; same accumulator contract. The gate
+// (stf_conv2d_dw_wide_ok): cout % 64 == 0, not stf_conv2d_dw_tall_ok,
+// c % 8 == 0, n*p*q % 64 == 0, n*p*q >= 768, a CS exists (a divisor of c, a
+// multiple of 8, r*s*CS <= 576, three LDS buffers of
+// 16 * (roundup(HR*HC*CS/8, 512) + 512) bytes within 160 KiB), and the 32-bit
+// offset limits. Every other implicit-path shape stays on
+// stf_conv2d_dw_splitk.
+int stf_conv2d_dw_wide_ok(const StfConvGeom* g);
+// plan = {CS, PW, PH, channel slices, cout slices, LDS bytes} of the launch;
+// returns 0 (plan untouched) outside the gate.
+int stf_conv2d_dw_wide_plan(const StfConvGeom* g, int plan[6]);
+hipError_t stf_conv2d_dw_wide(const void* x, const void* dy, void* dw_f32,
+                              const void* zero16, const StfConvGeom* g,
+                              hipStream_t stream);
 
 // ---- gemm_i8.hip ----
 // Quantized quint8 x quint8 -> qint32 on the i8 MFMA. Ranges are device f32

@@ -650,6 +650,55 @@ PYBIND11_MODULE(_core, m) {
     (void)hipFree(dev);
     return out;
   });
+  m.def("conv_dw_wide_plan", [](int n, int h, int w, int c, int r, int s,
+                                int64_t cout, int sh, int sw, int ph, int pw,
+                                int p, int q) -> py::object {
+    // The launch plan of hip/conv_dw_wide.hip for this geometry, from the
+    // host function the launch uses: (CS, PW, PH, channel slices, cout
+    // slices, LDS bytes), or None outside the kernel's gate. No GPU needed.
+    StfConvGeom g{n, h, w, c, r, s, sh, sw, ph, pw, p, q, cout};
+    int plan[6];
+    if (!stf_conv2d_dw_wide_plan(&g, plan)) return py::none();
+    return py::make_tuple(plan[0], plan[1], plan[2], plan[3], plan[4],
+                          plan[5]);
+  });
+  m.def("conv2d_dw_wide", [](py::array_t<uint16_t> x, py::array_t<uint16_t> dy,
+                             int r, int s, int sh, int sw, int ph, int pw) {
+    // One launch of hip/conv_dw_wide.hip on bf16 bits x [n,h,w,c] and
+    // dy [n,p,q,cout] into a zeroed accumulator: returns f32 [r*s*c, cout].
+    auto xa = py::array_t<uint16_t, py::array::c_style |
+                                        py::array::forcecast>(x);
+    auto da = py::array_t<uint16_t, py::array::c_style |
+                                        py::array::forcecast>(dy);
+    if (xa.ndim() != 4 || da.ndim() != 4 || xa.shape(0) != da.shape(0))
+      throw std::runtime_error("x: [n,h,w,c], dy: [n,p,q,cout] u16");
+    StfConvGeom g{(int)xa.shape(0), (int)xa.shape(1), (int)xa.shape(2),
+                  (int)xa.shape(3), r, s, sh, sw, ph, pw, (int)da.shape(1),
+                  (int)da.shape(2), (int64_t)da.shape(3)};
+    if (!stf_conv2d_dw_wide_ok(&g))
+      throw std::runtime_error("conv2d_dw_wide: shape outside the gate");
+    size_t xb = (size_t)xa.size() * 2, db = (size_t)da.size() * 2;
+    size_t rows = (size_t)r * s * g.c, ob = rows * (size_t)g.cout * 4;
+    py::array_t<float> out({(py::ssize_t)rows, (py::ssize_t)g.cout});
+    void *dx = nullptr, *dd = nullptr, *dacc = nullptr;  // dacc: zero page,
+                                                         // then accumulator
+    auto ok = [&](hipError_t e) {
+      if (e == hipSuccess) return;
+      (void)hipFree(dx); (void)hipFree(dd); (void)hipFree(dacc);
+      throw std::runtime_error(hipGetErrorString(e));
+    };
+    ok(hipMalloc(&dx, xb));
+    ok(hipMalloc(&dd, db));
+    ok(hipMalloc(&dacc, 256 + ob));
+    ok(hipMemcpy(dx, xa.data(), xb, hipMemcpyHostToDevice));
+    ok(hipMemcpy(dd, da.data(), db, hipMemcpyHostToDevice));
+    ok(hipMemset(dacc, 0, 256 + ob));
+    ok(stf_conv2d_dw_wide(dx, dd, (char*)dacc + 256, dacc, &g, nullptr));
+    ok(hipMemcpy(out.mutable_data(), (char*)dacc + 256, ob,
+                 hipMemcpyDeviceToHost));
+    (void)hipFree(dx); (void)hipFree(dd); (void)hipFree(dacc);
+    return out;
+  });
   m.def("rccl_get_unique_id", []() {
     return py::bytes(stf::RcclGetUniqueId());
   });

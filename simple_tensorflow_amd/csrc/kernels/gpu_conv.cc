@@ -383,6 +383,136 @@ class GpuConv2DBackpropFilterOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropFilter").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("filter_sizes"), GpuConv2DBackpropFilterOp);
 
 // ---------------------------------------------------------------------------
+// float32 Conv2D family: one f32-MFMA implicit-GEMM kernel (hip/conv_f32.hip)
+// for the forward and both gradients, any shape. Nothing is padded, packed or
+// cast, so there is one path per op.
+// ---------------------------------------------------------------------------
+// The kernel indexes with 32-bit offsets.
+static Status FitConvF32(const std::string& op, const StfConvGeom& sg) {
+  if (!stf_conv2d_f32_ok(&sg))
+    return errors::InvalidArgument(op, ": tensor sizes do not fit the f32 "
+                                   "GPU kernel's 32-bit offsets");
+  return Status::OK();
+}
+
+// The kernel reads dy as [N, P, Q, K] of the geometry: anything else would
+// be read out of bounds, so it is refused here.
+static Status CheckOutBackprop(const std::string& op, const TensorShape& dy,
+                               const ConvGeom& g) {
+  if (dy.dims() != 4 || dy.dim_size(0) != g.N || dy.dim_size(1) != g.P ||
+      dy.dim_size(2) != g.Q || dy.dim_size(3) != g.K)
+    return errors::InvalidArgument(op, ": out_backprop must be [", g.N, ", ",
+                                   g.P, ", ", g.Q, ", ", g.K, "]");
+  return Status::OK();
+}
+
+class GpuConv2DF32Op : public OpKernel {
+ public:
+  explicit GpuConv2DF32Op(OpKernelConstruction* c) : OpKernel(c), attrs_(c) {}
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& x = ctx->input(0);
+    const Tensor& w = ctx->input(1);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitConvF32(attrs_.op, sg));
+    Tensor* y = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, g.K}));
+    OP_HIP_OK(ctx, stf_conv2d_f32_fwd(x.raw_data(), w.raw_data(),
+                                      y->raw_data(), &sg, GPU_STREAM(ctx)));
+  }
+
+ private:
+  ConvAttrs attrs_;
+};
+REGISTER_KERNEL_BUILDER(Name("Conv2D").Device(DEVICE_GPU).TypeConstraint<float>("T"), GpuConv2DF32Op);
+
+class GpuConv2DBackpropInputF32Op : public OpKernel {
+ public:
+  explicit GpuConv2DBackpropInputF32Op(OpKernelConstruction* c,
+                                       bool side = false)
+      : OpKernel(c), attrs_(c), side_(side) {}
+  void Compute(OpKernelContext* ctx) override {
+    auto in_sizes = IntVector(ctx->input(0));
+    const Tensor& w = ctx->input(1);
+    const Tensor& dy = ctx->input(2);
+    TensorShape x_shape(in_sizes);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x_shape, w.shape(), attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitConvF32(attrs_.op, sg));
+    OP_REQUIRES_OK(ctx, CheckOutBackprop(attrs_.op, dy.shape(), g));
+    Tensor* dx = ctx->allocate_output(0, x_shape);
+    const void* side = nullptr;
+    if (side_) {
+      const Tensor& sd = ctx->input(3);
+      OP_REQUIRES(ctx, sd.NumElements() == dx->NumElements(),
+                  errors::InvalidArgument(
+                      "Conv2DBackpropInputAdd: side shape mismatch"));
+      side = sd.raw_data();
+    }
+    // the residual gradient is added in the kernel's epilogue, in f32
+    OP_HIP_OK(ctx, stf_conv2d_f32_dx(dy.raw_data(), w.raw_data(), side,
+                                     dx->raw_data(), &sg, GPU_STREAM(ctx)));
+  }
+
+ private:
+  ConvAttrs attrs_;
+  bool side_;
+};
+REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropInput").Device(DEVICE_GPU).TypeConstraint<float>("T").HostMemory("input_sizes"), GpuConv2DBackpropInputF32Op);
+
+class GpuConv2DBackpropInputAddF32Op : public GpuConv2DBackpropInputF32Op {
+ public:
+  explicit GpuConv2DBackpropInputAddF32Op(OpKernelConstruction* c)
+      : GpuConv2DBackpropInputF32Op(c, true) {}
+};
+REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropInputAdd").Device(DEVICE_GPU).TypeConstraint<float>("T").HostMemory("input_sizes"), GpuConv2DBackpropInputAddF32Op);
+
+// Slices of the n*p*q contraction so that the 128 x 64 tiles of dW give each
+// of the 256 CUs about one block (PickSplitK's idea), while a slice keeps at
+// least 8 of the kernel's k steps of 16 pixels. Every slice adds its whole
+// tile into dW with atomics, so more slices than CUs only add contention.
+static int PickConvF32DwSplits(const ConvGeom& g) {
+  int64_t tiles = ((g.RSC() + 127) / 128) * ((g.K + 63) / 64);
+  if (tiles == 0 || tiles >= 256) return 1;
+  int64_t by_work = g.M() / (8 * 16);
+  int64_t want = std::min<int64_t>(256 / tiles, by_work);
+  return (int)std::max<int64_t>(1, want);
+}
+
+class GpuConv2DBackpropFilterF32Op : public OpKernel {
+ public:
+  explicit GpuConv2DBackpropFilterF32Op(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
+  void Compute(OpKernelContext* ctx) override {
+    hipStream_t s = GPU_STREAM(ctx);
+    const Tensor& x = ctx->input(0);
+    auto f_sizes = IntVector(ctx->input(1));
+    const Tensor& dy = ctx->input(2);
+    TensorShape f_shape(f_sizes);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), f_shape, attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitConvF32(attrs_.op, sg));
+    OP_REQUIRES_OK(ctx, CheckOutBackprop(attrs_.op, dy.shape(), g));
+    Tensor* dw = ctx->allocate_output(0, f_shape);
+    // the blocks of a split launch add into dw itself: no arena, no cast.
+    // Zeroed by a kernel, not a memset: the step may be captured in a
+    // hipGraph, which is replayed without memset nodes here.
+    int splits = PickConvF32DwSplits(g);
+    if (splits > 1)
+      OP_HIP_OK(ctx, stf_fill_f32(dw->raw_data(), 0.f, dw->NumElements(), 0,
+                                  s));
+    OP_HIP_OK(ctx, stf_conv2d_f32_dw(x.raw_data(), dy.raw_data(),
+                                     dw->raw_data(), &sg, splits, s));
+  }
+
+ private:
+  ConvAttrs attrs_;
+};
+REGISTER_KERNEL_BUILDER(Name("Conv2DBackpropFilter").Device(DEVICE_GPU).TypeConstraint<float>("T").HostMemory("filter_sizes"), GpuConv2DBackpropFilterF32Op);
+
+// ---------------------------------------------------------------------------
 // depthwise conv (reference depthwise_conv_op_gpu.cu.cc family); g.K is the
 // channel multiplier of the [R, S, C, mult] filter
 // ---------------------------------------------------------------------------

@@ -148,6 +148,37 @@ hipError_t stf_conv2d_dw_wide(const void* x, const void* dy, void* dw_f32,
                               const void* zero16, const StfConvGeom* g,
                               hipStream_t stream);
 
+// ---- conv_f32.hip ----
+// float32 Conv2D and its two gradients as implicit GEMMs on the f32 MFMA:
+// f32 operands, f32 accumulation, f32 out, nothing rounded to bf16. x is
+// [n,h,w,c], w is [r,s,c,cout], y and dy are [n,p,q,cout]. No shape gate:
+// any c, cout, filter, stride and padding of a StfConvGeom; operands whose
+// contiguous extent is a multiple of 4 and whose base is 16-byte aligned are
+// read with 16-byte loads, the others element by element. Empty outputs
+// launch nothing.
+//
+// Offsets are 32-bit. stf_conv2d_f32_ok: the element counts of x, y and w
+// (and r*s*c, r*s*cout) stay below INT_MAX - 512, and max(c, cout) / 64
+// fits gridDim.y. The three launchers return hipErrorInvalidValue for a
+// geometry it refuses.
+int stf_conv2d_f32_ok(const StfConvGeom* g);
+// y = conv(x, w); every element of y is written.
+hipError_t stf_conv2d_f32_fwd(const void* x, const void* w, void* y,
+                              const StfConvGeom* g, hipStream_t stream);
+// dx = backprop-input(dy, w) (+ side_or_null, f32 of dx's shape, added in f32
+// in the epilogue); every element of dx is written. g is the forward
+// geometry; every stride runs the same gather, no column buffer.
+hipError_t stf_conv2d_f32_dx(const void* dy, const void* w,
+                             const void* side_or_null, void* dx,
+                             const StfConvGeom* g, hipStream_t stream);
+// dw = backprop-filter(x, dy), the n*p*q contraction cut into at most
+// `splits` slices (multiples of 16 pixels; fewer when there are not that many
+// steps). splits <= 1: every element of dw is stored. splits > 1: the blocks
+// atomicAdd, so the caller zeroes dw on the stream first.
+hipError_t stf_conv2d_f32_dw(const void* x, const void* dy, void* dw,
+                             const StfConvGeom* g, int splits,
+                             hipStream_t stream);
+
 // ---- gemm_i8.hip ----
 // Quantized quint8 x quint8 -> qint32 on the i8 MFMA. Ranges are device f32
 // scalars: zero points are derived on the device, min_out/max_out are

@@ -453,6 +453,67 @@ class CpuDepthwiseConvOp : public OpKernel {
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNative").Device(DEVICE_CPU).TypeConstraint<float>("T"), CpuDepthwiseConvOp<float>);
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNative").Device(DEVICE_CPU).TypeConstraint<bfloat16>("T"), CpuDepthwiseConvOp<bfloat16>);
 
+// Both gradients in one pass over the forward loop nest: every term
+// x * w of y is a term dy * w of dx and a term x * dy of dw. FILTER selects
+// which of the two is summed (in f32) and written.
+template <typename T, bool FILTER>
+class CpuDepthwiseConvBackpropOp : public OpKernel {
+ public:
+  explicit CpuDepthwiseConvBackpropOp(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
+  void Compute(OpKernelContext* ctx) override {
+    // BackpropInput: (input_sizes, filter, dy); BackpropFilter: (input,
+    // filter_sizes, dy). `other` is the operand that is not a shape.
+    const Tensor& other = ctx->input(FILTER ? 0 : 1);
+    const Tensor& sizes = ctx->input(FILTER ? 1 : 0);
+    const Tensor& dy = ctx->input(2);
+    TensorShape out_shape(IntVector(sizes));
+    const TensorShape& x_shape = FILTER ? other.shape() : out_shape;
+    const TensorShape& w_shape = FILTER ? out_shape : other.shape();
+    ConvGeom d;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x_shape, w_shape, attrs_, &d));
+    int64_t CM = d.C * d.K;
+    OP_REQUIRES(ctx, dy.dims() == 4 && dy.dim_size(0) == d.N &&
+                         dy.dim_size(1) == d.P && dy.dim_size(2) == d.Q &&
+                         dy.dim_size(3) == CM,
+                errors::InvalidArgument(attrs_.op, ": out_backprop must be [",
+                                        d.N, ", ", d.P, ", ", d.Q, ", ", CM,
+                                        "]"));
+    Tensor* out = ctx->allocate_output(0, out_shape);
+    const T* op = other.flat<T>();
+    const T* dyp = dy.flat<T>();
+    std::vector<float> acc(out_shape.num_elements(), 0.f);
+    for (int64_t n = 0; n < d.N; ++n)
+      for (int64_t p = 0; p < d.P; ++p)
+        for (int64_t q = 0; q < d.Q; ++q)
+          for (int64_t cm = 0; cm < CM; ++cm) {
+            int64_t c = cm / d.K;
+            float g = (float)dyp[((n * d.P + p) * d.Q + q) * CM + cm];
+            for (int64_t r = 0; r < d.R; ++r) {
+              int64_t ih = p * d.sh - d.ph + r;
+              if (ih < 0 || ih >= d.H) continue;
+              for (int64_t s2 = 0; s2 < d.S; ++s2) {
+                int64_t iw = q * d.sw - d.pw + s2;
+                if (iw < 0 || iw >= d.W) continue;
+                int64_t xi = ((n * d.H + ih) * d.W + iw) * d.C + c;
+                int64_t wi = (r * d.S + s2) * CM + cm;
+                if (FILTER) acc[wi] += (float)op[xi] * g;
+                else acc[xi] += (float)op[wi] * g;
+              }
+            }
+          }
+    T* outp = out->flat<T>();
+    for (size_t i = 0; i < acc.size(); ++i) outp[i] = (T)acc[i];
+  }
+
+ private:
+  ConvAttrs attrs_;
+};
+REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropInput").Device(DEVICE_CPU).TypeConstraint<float>("T"), CpuDepthwiseConvBackpropOp<float, false>);
+REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropInput").Device(DEVICE_CPU).TypeConstraint<bfloat16>("T"), CpuDepthwiseConvBackpropOp<bfloat16, false>);
+REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropFilter").Device(DEVICE_CPU).TypeConstraint<float>("T"), CpuDepthwiseConvBackpropOp<float, true>);
+REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropFilter").Device(DEVICE_CPU).TypeConstraint<bfloat16>("T"), CpuDepthwiseConvBackpropOp<bfloat16, true>);
+
 // Local response normalization over the channel (last) axis:
 // y_i = x_i / (bias + alpha * sum_{|j-i|<=r} x_j^2)^beta
 // (reference lrn_op.cc; the backward pass is a python composite in

@@ -592,5 +592,117 @@ class GpuDepthwiseConvBackpropFilterOp : public OpKernel {
 };
 REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropFilter").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T").HostMemory("filter_sizes"), GpuDepthwiseConvBackpropFilterOp);
 
+// ---------------------------------------------------------------------------
+// float32 depthwise conv family: the tiled kernels of hip/depthwise_f32.hip,
+// any shape, f32 in and out. Nothing is cast and dW needs no scratch.
+// ---------------------------------------------------------------------------
+static Status FitDepthwiseF32(const std::string& op, const ConvGeom& g,
+                              const StfConvGeom& sg) {
+  STF_RETURN_IF_ERROR(FitInt(op, {g.K, g.C * g.K}));  // passed as int mult
+  if (!stf_depthwise_f32_ok(&sg, (int)g.K))
+    return errors::InvalidArgument(op, ": tensor or filter sizes do not fit "
+                                   "the f32 GPU kernel's tiles and 32-bit "
+                                   "offsets");
+  return Status::OK();
+}
+
+// dy as the kernels read it: [N, P, Q, C * mult].
+static Status CheckDepthwiseOutBackprop(const std::string& op,
+                                        const TensorShape& dy, ConvGeom g) {
+  g.K *= g.C;
+  return CheckOutBackprop(op, dy, g);
+}
+
+class GpuDepthwiseConvF32Op : public OpKernel {
+ public:
+  explicit GpuDepthwiseConvF32Op(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& x = ctx->input(0);
+    const Tensor& w = ctx->input(1);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitDepthwiseF32(attrs_.op, g, sg));
+    Tensor* y = ctx->allocate_output(
+        0, TensorShape({g.N, g.P, g.Q, g.C * g.K}));
+    OP_HIP_OK(ctx, stf_depthwise_f32_fwd(x.raw_data(), w.raw_data(),
+                                         y->raw_data(), &sg, (int)g.K,
+                                         GPU_STREAM(ctx)));
+  }
+
+ private:
+  ConvAttrs attrs_;
+};
+REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNative").Device(DEVICE_GPU).TypeConstraint<float>("T"), GpuDepthwiseConvF32Op);
+
+class GpuDepthwiseConvBackpropInputF32Op : public OpKernel {
+ public:
+  explicit GpuDepthwiseConvBackpropInputF32Op(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
+  void Compute(OpKernelContext* ctx) override {
+    auto in_sizes = IntVector(ctx->input(0));
+    const Tensor& w = ctx->input(1);
+    const Tensor& dy = ctx->input(2);
+    TensorShape x_shape(in_sizes);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x_shape, w.shape(), attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitDepthwiseF32(attrs_.op, g, sg));
+    OP_REQUIRES_OK(ctx, CheckDepthwiseOutBackprop(attrs_.op, dy.shape(), g));
+    Tensor* dx = ctx->allocate_output(0, x_shape);
+    OP_HIP_OK(ctx, stf_depthwise_f32_dx(dy.raw_data(), w.raw_data(),
+                                        dx->raw_data(), &sg, (int)g.K,
+                                        GPU_STREAM(ctx)));
+  }
+
+ private:
+  ConvAttrs attrs_;
+};
+REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropInput").Device(DEVICE_GPU).TypeConstraint<float>("T").HostMemory("input_sizes"), GpuDepthwiseConvBackpropInputF32Op);
+
+// Persistent dW blocks per slice of 32 channels: about two blocks per CU over
+// all slices, while a worker keeps at least 256 output pixels (two patches),
+// below which its final reduction and atomics cost more than its loop. The
+// kernel caps the count at the number of patches.
+static int PickDepthwiseF32Workers(const ConvGeom& g) {
+  int64_t slices = std::max<int64_t>(1, (g.C * g.K + 31) / 32);
+  int64_t by_work = g.M() / 256;
+  int64_t want = std::min<int64_t>((2 * 256 + slices - 1) / slices, by_work);
+  return (int)std::max<int64_t>(1, want);
+}
+
+class GpuDepthwiseConvBackpropFilterF32Op : public OpKernel {
+ public:
+  explicit GpuDepthwiseConvBackpropFilterF32Op(OpKernelConstruction* c)
+      : OpKernel(c), attrs_(c) {}
+  void Compute(OpKernelContext* ctx) override {
+    hipStream_t s = GPU_STREAM(ctx);
+    const Tensor& x = ctx->input(0);
+    auto f_sizes = IntVector(ctx->input(1));
+    const Tensor& dy = ctx->input(2);
+    TensorShape f_shape(f_sizes);
+    ConvGeom g;
+    StfConvGeom sg;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), f_shape, attrs_, &g, &sg));
+    OP_REQUIRES_OK(ctx, FitDepthwiseF32(attrs_.op, g, sg));
+    OP_REQUIRES_OK(ctx, CheckDepthwiseOutBackprop(attrs_.op, dy.shape(), g));
+    Tensor* dw = ctx->allocate_output(0, f_shape);
+    // several workers add into dw itself, zeroed by a kernel for the reason
+    // given in GpuConv2DBackpropFilterF32Op; one worker stores
+    int workers = PickDepthwiseF32Workers(g);
+    if (workers > 1)
+      OP_HIP_OK(ctx, stf_fill_f32(dw->raw_data(), 0.f, dw->NumElements(), 0,
+                                  s));
+    OP_HIP_OK(ctx, stf_depthwise_f32_dw(x.raw_data(), dy.raw_data(),
+                                        dw->raw_data(), &sg, (int)g.K,
+                                        workers, s));
+  }
+
+ private:
+  ConvAttrs attrs_;
+};
+REGISTER_KERNEL_BUILDER(Name("DepthwiseConv2dNativeBackpropFilter").Device(DEVICE_GPU).TypeConstraint<float>("T").HostMemory("filter_sizes"), GpuDepthwiseConvBackpropFilterF32Op);
+
 }  // namespace
 }  // namespace stf

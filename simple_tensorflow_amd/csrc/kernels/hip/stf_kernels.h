@@ -337,6 +337,36 @@ hipError_t stf_depthwise_bwd_filter(const void* x, const void* dy,
                                     float* dw_f32, const StfConvGeom* g,
                                     int mult, hipStream_t stream);
 
+// ---- depthwise_f32.hip ----
+// float32 depthwise conv and its two gradients, tiled through LDS: f32 in,
+// f32 accumulation, f32 out. x is [n,h,w,c], the filter [r,s,c,mult], y and
+// dy are [n,p,q,c*mult]; g->cout is unused. Any c, mult, filter, stride and
+// padding: mult == 1 with c % 4 == 0 and 16-byte aligned bases moves 16 bytes
+// per lane, everything else 4. Empty outputs launch nothing.
+//
+// stf_depthwise_f32_ok: one image of x and of y, and r*s*c*mult, stay below
+// INT_MAX - 64 elements (offsets are a 64-bit image base plus 32 bits), the
+// block count fits gridDim.x, and one output row's halo of 32 channels plus
+// the filter slice fits 64 KiB of LDS. The three launchers return
+// hipErrorInvalidValue for a geometry it refuses.
+int stf_depthwise_f32_ok(const StfConvGeom* g, int mult);
+// y = depthwise(x, w); every element of y is written.
+hipError_t stf_depthwise_f32_fwd(const void* x, const void* w, void* y,
+                                 const StfConvGeom* g, int mult,
+                                 hipStream_t stream);
+// dx = backprop-input(dy, w); every element of dx is written. g is the
+// forward geometry.
+hipError_t stf_depthwise_f32_dx(const void* dy, const void* w, void* dx,
+                                const StfConvGeom* g, int mult,
+                                hipStream_t stream);
+// dw = backprop-filter(x, dy) by at most `workers` persistent blocks per
+// slice of 32 channels. workers <= 1: every element of dw is stored.
+// workers > 1: each block adds its sums with one atomicAdd per filter
+// element, so the caller zeroes dw on the stream first.
+hipError_t stf_depthwise_f32_dw(const void* x, const void* dy, void* dw,
+                                const StfConvGeom* g, int mult, int workers,
+                                hipStream_t stream);
+
 // ---- elementwise.hip ----
 hipError_t stf_unary(int op, int dtype, const void* x, void* y, int64_t n,
                      hipStream_t stream);

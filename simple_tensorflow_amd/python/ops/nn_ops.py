@@ -219,7 +219,8 @@ local_response_normalization = lrn
 
 def depthwise_conv2d(input, filter, strides, padding, rate=None, name=None):  # pylint: disable=redefined-builtin
     """Depthwise 2-D convolution (reference nn_impl.depthwise_conv2d;
-    kernels in csrc/kernels/hip/depthwise.hip)."""
+    GPU kernels: float32 in csrc/kernels/hip/depthwise_f32.hip, bfloat16 in
+    csrc/kernels/hip/depthwise.hip)."""
     x = convert_to_tensor(input)
     w = convert_to_tensor(filter)
     out = apply_op('DepthwiseConv2dNative', x, w,

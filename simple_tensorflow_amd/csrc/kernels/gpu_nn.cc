@@ -339,7 +339,11 @@ REGISTER_KERNEL_BUILDER(Name("AvgPool").Device(DEVICE_GPU).TypeConstraint<bfloat
 
 class GpuMaxPoolGradOp : public OpKernel {
  public:
-  explicit GpuMaxPoolGradOp(OpKernelConstruction* c) : OpKernel(c), p_(c) {}
+  explicit GpuMaxPoolGradOp(OpKernelConstruction* c) : OpKernel(c), p_(c) {
+    // STF_NO_TILED_MAXPOOL_GRAD (A/B runs) keeps 3x3/2 on the per-input
+    // kernel. Read per kernel, so a new graph sees a changed setting.
+    tiled_ = getenv("STF_NO_TILED_MAXPOOL_GRAD") == nullptr;
+  }
   void Compute(OpKernelContext* ctx) override {
     const Tensor& x = ctx->input(0);
     const Tensor& dy = ctx->input(2);
@@ -350,7 +354,7 @@ class GpuMaxPoolGradOp : public OpKernel {
     if (x.dtype() == DT_BFLOAT16 && g.C % 8 == 0) {
       // per-input direct path: no f32 scratch, no zero fill, no cast
       OP_HIP_OK(ctx, stf_max_pool_bwd_v8(x.raw_data(), dy.raw_data(),
-                                         dx->raw_data(), &g, s));
+                                         dx->raw_data(), &g, tiled_, s));
       return;
     }
     Tensor scratch = ctx->allocate_temp(DT_FLOAT, x.shape());
@@ -364,6 +368,7 @@ class GpuMaxPoolGradOp : public OpKernel {
 
  private:
   PoolAttrs p_;
+  bool tiled_;
 };
 REGISTER_KERNEL_BUILDER(Name("MaxPoolGrad").Device(DEVICE_GPU).TypeConstraint<float>("T"), GpuMaxPoolGradOp);
 REGISTER_KERNEL_BUILDER(Name("MaxPoolGrad").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuMaxPoolGradOp);

@@ -468,9 +468,12 @@ hipError_t stf_pool_fwd(int dtype, int is_max, const void* x, void* y,
 hipError_t stf_max_pool_bwd(int dtype, const void* x, const void* dy,
                             float* dx_f32, const StfPoolGeom* g,
                             hipStream_t stream);
-// bf16, C % 8 == 0: writes dx directly, no scratch.
+// bf16, C % 8 == 0: writes every element of dx directly, no scratch. With
+// tiled != 0, 3x3 windows of stride 2 run MaxPoolGradTiled, which gives the
+// same bits as the per-input kernel every other geometry runs.
 hipError_t stf_max_pool_bwd_v8(const void* x, const void* dy, void* dx_bf16,
-                               const StfPoolGeom* g, hipStream_t stream);
+                               const StfPoolGeom* g, int tiled,
+                               hipStream_t stream);
 hipError_t stf_avg_pool_bwd(int dtype, const void* dy, void* dx,
                             const StfPoolGeom* g, hipStream_t stream);
 

@@ -21,6 +21,11 @@ void ParseArgSpec(const std::string& spec, OpDef::ArgDef* arg) {
   if (star != std::string::npos) {
     arg->number_attr = StrStrip(type.substr(0, star));
     type = StrStrip(type.substr(star + 1));
+    if (StrStartsWith(type, "Ref(")) {  // "N * Ref(T)"
+      CHECK(type.back() == ')') << "bad arg spec: " << spec;
+      arg->is_ref = true;
+      type = StrStrip(type.substr(4, type.size() - 5));
+    }
   }
   DataType dt = DataTypeFromString(type);
   if (dt != DT_INVALID) {

@@ -279,6 +279,10 @@ REGISTER_OP("ScatterSub").Input("ref: Ref(T)").Input("indices: Tindices").Input(
 REGISTER_OP("ScatterAdd").Input("ref: Ref(T)").Input("indices: Tindices").Input("updates: T").Output("output_ref: Ref(T)").Attr("T: " NUMTYPES).Attr("Tindices: {int32, int64}").Attr("use_locking: bool = false");
 REGISTER_OP("ApplyGradientDescent").Input("var: Ref(T)").Input("alpha: T").Input("delta: T").Output("out: Ref(T)").Attr("T: " FLOATTYPES).Attr("use_locking: bool = false");
 REGISTER_OP("ApplyMomentum").Input("var: Ref(T)").Input("accum: Ref(T)").Input("lr: T").Input("grad: T").Input("momentum: T").Output("out: Ref(T)").Attr("T: " FLOATTYPES).Attr("use_locking: bool = false").Attr("use_nesterov: bool = false");
+// Internal (graph/optimizer.cc FuseApplyMomentum): N ApplyMomentum updates of
+// f32 variables as one GPU-only node, all gradients of the one type G. No
+// outputs: what waited for the members waits for it through control edges.
+REGISTER_OP("_MultiApplyMomentum").Input("vars: N * Ref(float)").Input("accums: N * Ref(float)").Input("lr: float").Input("grads: N * G").Input("momentum: float").Attr("N: int >= 1").Attr("G: {float, bfloat16}").Attr("use_nesterov: bool = false").SetIsStateful();
 REGISTER_OP("ApplyAdam").Input("var: Ref(T)").Input("m: Ref(T)").Input("v: Ref(T)").Input("beta1_power: T").Input("beta2_power: T").Input("lr: T").Input("beta1: T").Input("beta2: T").Input("epsilon: T").Input("grad: T").Output("out: Ref(T)").Attr("T: " FLOATTYPES).Attr("use_locking: bool = false");
 REGISTER_OP("ApplyRMSProp").Input("var: Ref(T)").Input("ms: Ref(T)").Input("mom: Ref(T)").Input("lr: T").Input("rho: T").Input("momentum: T").Input("epsilon: T").Input("grad: T").Output("out: Ref(T)").Attr("T: " FLOATTYPES).Attr("use_locking: bool = false");
 REGISTER_OP("ApplyAdagrad").Input("var: Ref(T)").Input("accum: Ref(T)").Input("lr: T").Input("grad: T").Output("out: Ref(T)").Attr("T: " FLOATTYPES).Attr("use_locking: bool = false");

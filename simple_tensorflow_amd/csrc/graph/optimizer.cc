@@ -509,6 +509,158 @@ int FuseConvBnStats(Graph* g, const std::set<std::string>& preserve,
   return fused;
 }
 
+// -------------------- multi-tensor ApplyMomentum fusion ---------------------
+// The ApplyMomentum nodes of one optimizer become one _MultiApplyMomentum,
+// whose kernel updates all their variables in a few launches. Members share
+// the GPU placement request, the lr and momentum sources (node and port),
+// use_nesterov, the gradient type and the set of nodes their control edges
+// lead to. This pass sees the whole graph, before it is pruned to what a run
+// fetches, and equal lr and momentum constants of unrelated optimizers have
+// been merged by then: a member is reached by exactly the runs that reach one
+// of the nodes waiting for it (a run that names the member itself preserves
+// it), so members with the same waiters are run together or not at all, and
+// the updates of another train op never ride along. The gradient type is
+// taken after looking through a bf16 -> f32 Cast that feeds only this update:
+// the kernel converts the bf16 gradient itself, so the Cast goes and its input
+// is wired in. An update stays as it is if it is preserved, if anything reads
+// its output as data, if nothing waits for it, if its var or accum is also an
+// input of another
+// ApplyMomentum, or if a path leads to it from another member (fusing the two
+// would close a cycle). Control edges of the members move to the fused node.
+using Port = std::pair<Node*, int>;
+
+struct MomentumMember {
+  Node* node = nullptr;
+  Node* cast = nullptr;  // the looked-through Cast, or nullptr
+  Port var, accum, lr, grad, mom;
+};
+
+bool OnlyFeeds(const Node* n, const Node* consumer) {
+  return n->out_edges.size() == 1 && n->out_edges[0]->dst == consumer &&
+         !n->out_edges[0]->IsControl();
+}
+
+int FuseApplyMomentum(Graph* g, const std::set<std::string>& preserve,
+                      bool have_gpu) {
+  // how many ApplyMomentum inputs each variable or slot ref is
+  std::map<Port, int> ref_uses;
+  std::vector<Node*> applies;
+  for (Node* n : g->nodes()) {
+    if (n->op() != "ApplyMomentum") continue;
+    applies.push_back(n);
+    for (int i = 0; i < 2; ++i)
+      if (const Edge* e = n->input_edge(i)) ++ref_uses[{e->src, e->src_output}];
+  }
+
+  // group key -> members, in node order
+  std::map<std::string, std::vector<MomentumMember>> groups;
+  for (Node* n : applies) {
+    if (preserve.count(n->name()) || n->in_types[0] != DT_FLOAT) continue;
+    std::string where = GpuPlacementKey(n, have_gpu);
+    if (where.empty()) continue;
+    bool data_consumer = false;
+    std::set<std::string> waiters;  // the nodes its control edges lead to
+    for (const Edge* e : n->out_edges) {
+      data_consumer |= !e->IsControl();
+      waiters.insert(e->dst->name());
+    }
+    // With nothing waiting for it, only a run that names it reaches it.
+    if (data_consumer || waiters.empty()) continue;
+    const Edge* in[5];
+    bool ok = true;
+    for (int i = 0; i < 5; ++i) ok &= (in[i] = n->input_edge(i)) != nullptr;
+    if (!ok) continue;
+    MomentumMember m;
+    m.node = n;
+    m.var = {in[0]->src, in[0]->src_output};
+    m.accum = {in[1]->src, in[1]->src_output};
+    m.lr = {in[2]->src, in[2]->src_output};
+    m.grad = {in[3]->src, in[3]->src_output};
+    m.mom = {in[4]->src, in[4]->src_output};
+    // var and accum are variables that placement will put where n goes
+    for (const Port& p : {m.var, m.accum})
+      ok &= p.second < (int)p.first->out_is_ref.size() &&
+            p.first->out_is_ref[p.second] && ref_uses[p] == 1 &&
+            GpuPlacementKey(p.first, have_gpu) == where;
+    if (!ok) continue;
+    DataType gt = DT_FLOAT;
+    Node* c = m.grad.first;
+    if (c->op() == "Cast" && c->in_types[0] == DT_BFLOAT16 &&
+        c->out_types[0] == DT_FLOAT && !preserve.count(c->name()) &&
+        OnlyFeeds(c, n) && c->in_edges.size() == 1 &&
+        GpuPlacementKey(c, have_gpu) == where) {
+      const Edge* ce = c->input_edge(0);
+      if (ce) {
+        m.cast = c;
+        m.grad = {ce->src, ce->src_output};
+        gt = DT_BFLOAT16;
+      }
+    }
+    bool nesterov = false;
+    GetAttrBool(n->def, "use_nesterov", &nesterov);
+    std::string key = where + '\0' + m.lr.first->name() + ':' +
+                      std::to_string(m.lr.second) + '\0' +
+                      m.mom.first->name() + ':' + std::to_string(m.mom.second) +
+                      '\0' + (nesterov ? 'n' : 'p') +
+                      (gt == DT_BFLOAT16 ? 'b' : 'f');
+    for (const std::string& w : waiters) key += '\0' + w;
+    groups[key].push_back(m);
+  }
+
+  int fused = 0;
+  for (auto& kv : groups) {
+    std::vector<MomentumMember>& members = kv.second;
+    if (members.size() < 2) continue;
+    // Everything downstream of a member. A member found there depends on
+    // another one and is left out; those that remain do not reach each other.
+    std::set<Node*> downstream;
+    std::vector<Node*> stack;
+    for (auto& m : members)
+      for (const Edge* e : m.node->out_edges) stack.push_back(e->dst);
+    while (!stack.empty()) {
+      Node* n = stack.back();
+      stack.pop_back();
+      if (!downstream.insert(n).second) continue;
+      for (const Edge* e : n->out_edges) stack.push_back(e->dst);
+    }
+    std::vector<MomentumMember> keep;
+    for (auto& m : members)
+      if (!downstream.count(m.node)) keep.push_back(m);
+    if (keep.size() < 2) continue;
+
+    const Node* first = keep[0].node;
+    const int n = (int)keep.size();
+    NodeDef def;
+    def.name = first->name() + "/_multi";
+    def.op = "_MultiApplyMomentum";
+    def.device = first->def.device;
+    def.attr["N"] = AttrValue::I(n);
+    def.attr["G"] = AttrValue::Type(keep[0].cast ? DT_BFLOAT16 : DT_FLOAT);
+    auto nest = first->def.attr.find("use_nesterov");
+    if (nest != first->def.attr.end()) def.attr["use_nesterov"] = nest->second;
+    Node* multi = nullptr;
+    if (!g->AddNode(def, &multi).ok()) continue;
+    g->AddEdge(keep[0].lr.first, keep[0].lr.second, multi, 2 * n);
+    g->AddEdge(keep[0].mom.first, keep[0].mom.second, multi, 3 * n + 1);
+    std::set<Node*> ctrl_in, ctrl_out;
+    for (int i = 0; i < n; ++i) {
+      const MomentumMember& m = keep[i];
+      g->AddEdge(m.var.first, m.var.second, multi, i);
+      g->AddEdge(m.accum.first, m.accum.second, multi, n + i);
+      g->AddEdge(m.grad.first, m.grad.second, multi, 2 * n + 1 + i);
+      for (const Edge* e : m.node->in_edges)
+        if (e->IsControl() && ctrl_in.insert(e->src).second)
+          g->AddControlEdge(e->src, multi);
+      for (const Edge* e : m.node->out_edges)
+        if (ctrl_out.insert(e->dst).second) g->AddControlEdge(multi, e->dst);
+      g->RemoveNode(m.node);
+      if (m.cast) g->RemoveNode(m.cast);
+    }
+    fused += n;
+  }
+  return fused;
+}
+
 }  // namespace
 
 // Runs CSE + constant folding to fixpoint (preserving feed/fetch/target
@@ -529,6 +681,8 @@ int OptimizeGraph(Graph* g, Device* cpu,
   // Read per call (A/B runs): one process can build a session each way.
   if (getenv("STF_NO_CONV_BN_STATS") == nullptr)
     total += FuseConvBnStats(g, preserve, have_gpu);
+  if (getenv("STF_NO_MULTI_APPLY") == nullptr)
+    total += FuseApplyMomentum(g, preserve, have_gpu);
   return total;
 }
 

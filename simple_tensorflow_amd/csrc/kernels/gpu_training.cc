@@ -81,6 +81,59 @@ class GpuApplyMomentumOp : public OpKernel {
 };
 REGISTER_KERNEL_BUILDER(Name("ApplyMomentum").Device(DEVICE_GPU).TypeConstraint<float>("T"), GpuApplyMomentumOp);
 
+// _MultiApplyMomentum (graph/optimizer.cc FuseApplyMomentum): N ApplyMomentum
+// updates in as few launches as the kernel's tables allow. Inputs: vars
+// [0, N), accums [N, 2N), lr 2N, grads [2N+1, 3N+1), momentum 3N+1.
+class GpuMultiApplyMomentumOp : public OpKernel {
+ public:
+  explicit GpuMultiApplyMomentumOp(OpKernelConstruction* c) : OpKernel(c) {
+    int64_t n = 0;
+    c->GetAttr("N", &n);
+    n_ = (int)n;
+    c->GetAttr("use_nesterov", &nesterov_);
+  }
+  void Compute(OpKernelContext* ctx) override {
+    const int n = n_;
+    OP_REQUIRES(ctx, ctx->num_inputs() == 3 * n + 2,
+                errors::InvalidArgument("_MultiApplyMomentum: ", 3 * n + 2,
+                                        " inputs expected"));
+    const DataType gt = ctx->input(2 * n + 1).dtype();
+    std::vector<void*> vars(n), accums(n);
+    std::vector<const void*> grads(n);
+    std::vector<int64_t> sizes(n);
+    for (int i = 0; i < n; ++i) {
+      Tensor var = ctx->input(i);
+      Tensor accum = ctx->input(n + i);
+      const Tensor& grad = ctx->input(2 * n + 1 + i);
+      OP_REQUIRES(ctx,
+                  var.dtype() == DT_FLOAT && accum.dtype() == DT_FLOAT &&
+                      grad.dtype() == gt,
+                  errors::InvalidArgument("_MultiApplyMomentum: dtype of ",
+                                          "variable ", i));
+      OP_REQUIRES(ctx,
+                  var.shape() == accum.shape() && var.shape() == grad.shape(),
+                  errors::InvalidArgument("_MultiApplyMomentum: var, accum ",
+                                          "and grad shapes differ at ", i));
+      vars[i] = var.raw_data();
+      accums[i] = accum.raw_data();
+      grads[i] = grad.raw_data();
+      sizes[i] = var.NumElements();
+    }
+    OP_HIP_OK(ctx, stf_multi_apply_momentum(
+                       gt == DT_BFLOAT16, n, vars.data(), accums.data(),
+                       grads.data(), sizes.data(),
+                       ctx->input(2 * n).raw_data(),
+                       ctx->input(3 * n + 1).raw_data(), nesterov_,
+                       GPU_STREAM(ctx)));
+  }
+
+ private:
+  int n_ = 0;
+  bool nesterov_ = false;
+};
+REGISTER_KERNEL_BUILDER(Name("_MultiApplyMomentum").Device(DEVICE_GPU).TypeConstraint<float>("G"), GpuMultiApplyMomentumOp);
+REGISTER_KERNEL_BUILDER(Name("_MultiApplyMomentum").Device(DEVICE_GPU).TypeConstraint<bfloat16>("G"), GpuMultiApplyMomentumOp);
+
 class GpuApplyAdamOp : public OpKernel {
  public:
   using OpKernel::OpKernel;

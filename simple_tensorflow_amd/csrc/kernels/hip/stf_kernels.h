@@ -530,6 +530,18 @@ hipError_t stf_apply_momentum(int grad_bf16, void* var, void* accum,
                               const void* lr, const void* grad,
                               const void* momentum, int nesterov, int64_t n,
                               hipStream_t stream);
+// stf_apply_momentum on `count` variables at once, bit-equal to it: tensor i
+// has sizes[i] elements at vars[i], accums[i] and grads[i] (host arrays of
+// device pointers; all gradients of the one type). Issues as few launches as
+// the table capacities of multi_apply_pack.h allow; tensors, chunks and
+// pointers travel in the kernel arguments, so the host arrays are free again
+// on return. hipErrorInvalidValue, with nothing launched, for a negative size.
+hipError_t stf_multi_apply_momentum(int grad_bf16, int count,
+                                    void* const* vars, void* const* accums,
+                                    const void* const* grads,
+                                    const int64_t* sizes, const void* lr,
+                                    const void* momentum, int nesterov,
+                                    hipStream_t stream);
 hipError_t stf_apply_adam(int grad_bf16, void* var, void* m, void* v,
                           const void* b1p, const void* b2p, const void* lr,
                           const void* b1, const void* b2, const void* eps,

@@ -241,6 +241,8 @@ REGISTER_OP("QuantizedMatMul").Input("a: T1").Input("b: T2").Input("min_a: float
 REGISTER_OP("QuantizedConv2D").Input("input: T1").Input("filter: T2").Input("min_input: float").Input("max_input: float").Input("min_filter: float").Input("max_filter: float").Output("output: out_type").Output("min_output: float").Output("max_output: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("out_type: {int32} = int32").Attr("strides: list(int)").Attr("padding: string");
 REGISTER_OP("QuantizedConv2DWithBiasAndRequantize").Input("input: T1").Input("filter: T2").Input("bias: float").Input("min_input: float").Input("max_input: float").Input("min_filter: float").Input("max_filter: float").Input("requested_output_min: float").Input("requested_output_max: float").Output("output: out_type").Output("min_output: float").Output("max_output: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("out_type: {uint8} = uint8").Attr("strides: list(int)").Attr("padding: string").Attr("activation: string = 'None'");
 REGISTER_OP("QuantizedConv2DWithBiasSumAndRequantize").Input("input: T1").Input("filter: T2").Input("bias: float").Input("summand: T1").Input("min_input: float").Input("max_input: float").Input("min_filter: float").Input("max_filter: float").Input("min_summand: float").Input("max_summand: float").Input("requested_output_min: float").Input("requested_output_max: float").Output("output: out_type").Output("min_output: float").Output("max_output: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("out_type: {uint8} = uint8").Attr("strides: list(int)").Attr("padding: string").Attr("activation: string = 'None'");
+REGISTER_OP("QuantizedDepthwiseConv2D").Input("input: T1").Input("filter: T2").Input("min_input: float").Input("max_input: float").Input("min_filter: float").Input("max_filter: float").Output("output: out_type").Output("min_output: float").Output("max_output: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("out_type: {int32} = int32").Attr("strides: list(int)").Attr("padding: string");
+REGISTER_OP("QuantizedDepthwiseConv2DWithBiasAndRequantize").Input("input: T1").Input("filter: T2").Input("bias: float").Input("min_input: float").Input("max_input: float").Input("min_filter: float").Input("max_filter: float").Input("requested_output_min: float").Input("requested_output_max: float").Output("output: out_type").Output("min_output: float").Output("max_output: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("out_type: {uint8} = uint8").Attr("strides: list(int)").Attr("padding: string").Attr("activation: string = 'None'");
 REGISTER_OP("QuantizedMatMulWithBiasAndRequantize").Input("a: T1").Input("b: T2").Input("bias: float").Input("min_a: float").Input("max_a: float").Input("min_b: float").Input("max_b: float").Input("requested_output_min: float").Input("requested_output_max: float").Output("out: Toutput").Output("min_out: float").Output("max_out: float").Attr("T1: {uint8} = uint8").Attr("T2: {uint8} = uint8").Attr("Toutput: {uint8} = uint8").Attr("transpose_a: bool = false").Attr("transpose_b: bool = false").Attr("activation: string = 'None'");
 REGISTER_OP("QuantizedRelu").Input("features: T").Input("min_features: float").Input("max_features: float").Output("activations: T").Output("min_activations: float").Output("max_activations: float").Attr("T: {uint8} = uint8");
 REGISTER_OP("QuantizeDownAndShrinkRange").Input("input: Tinput").Input("input_min: float").Input("input_max: float").Output("output: out_type").Output("output_min: float").Output("output_max: float").Attr("Tinput: {int32} = int32").Attr("out_type: {uint8} = uint8");

@@ -322,6 +322,105 @@ REGISTER_KERNEL_BUILDER(
     Name("QuantizedConv2DWithBiasSumAndRequantize").Device(DEVICE_CPU),
     QuantizedConv2DFusedSumOp);
 
+// out[n,p,q,c*K+m] = sum over the taps inside the image of
+// (x[n,ih,iw,c] - z_in) * (w[r,s,c,m] - z_f), NHWC input, [R,S,C,K] filter
+// with K the channel multiplier, reduced to int32 modulo 2^32. Zero points
+// and the output range follow QuantizedConv2D. This is the definition that
+// kernels/hip/depthwise_q8.hip equals.
+// QuantizedDepthwiseConv2DWithBiasAndRequantize (fused) sends the same sums
+// through the fused epilogue: inputs input, filter, bias [C*K], the four
+// ranges, the requested output range; quint8 output.
+template <class Sink>
+void QuantDepthwiseLoop(const ConvGeom& g, const uint8_t* xp,
+                        const uint8_t* wp, int32_t zx, int32_t zf, Sink sink) {
+  const int64_t CM = g.C * g.K;
+  std::vector<int64_t> acc(CM);
+  for (int64_t n = 0; n < g.N; ++n)
+    for (int64_t p = 0; p < g.P; ++p)
+      for (int64_t q = 0; q < g.Q; ++q) {
+        std::fill(acc.begin(), acc.end(), 0);
+        for (int64_t r = 0; r < g.R; ++r) {
+          int64_t h = p * g.sh - g.ph + r;
+          if (h < 0 || h >= g.H) continue;
+          for (int64_t s = 0; s < g.S; ++s) {
+            int64_t wi = q * g.sw - g.pw + s;
+            if (wi < 0 || wi >= g.W) continue;
+            const uint8_t* xr = xp + ((n * g.H + h) * g.W + wi) * g.C;
+            const uint8_t* wr = wp + (r * g.S + s) * CM;
+            for (int64_t c = 0; c < g.C; ++c) {
+              int64_t xv = (int32_t)xr[c] - zx;
+              for (int64_t m = 0; m < g.K; ++m)
+                acc[c * g.K + m] += xv * ((int32_t)wr[c * g.K + m] - zf);
+            }
+          }
+        }
+        int64_t o = ((n * g.P + p) * g.Q + q) * CM;
+        for (int64_t k = 0; k < CM; ++k) sink(o + k, k, (int32_t)acc[k]);
+      }
+}
+
+class QuantizedDepthwiseConv2DOp : public OpKernel {
+ public:
+  QuantizedDepthwiseConv2DOp(OpKernelConstruction* c, bool fused)
+      : OpKernel(c), fused_(fused), attrs_(c) {
+    if (fused_) act_ = QuantFusedActivation(c);
+  }
+  explicit QuantizedDepthwiseConv2DOp(OpKernelConstruction* c)
+      : QuantizedDepthwiseConv2DOp(c, false) {}
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& x = ctx->input(0);
+    const Tensor& w = ctx->input(1);
+    ConvGeom g;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &g));
+    int64_t cm;
+    OP_REQUIRES_OK(ctx, QuantDepthwiseChannels(attrs_.op, g.C, g.K, &cm));
+    if (fused_)
+      OP_REQUIRES_OK(ctx, QuantFusedBiasDims(attrs_.op,
+                                             ctx->input(2).shape(), cm));
+    int r = fused_ ? 3 : 2;  // the first range input
+    float min_x = RangeIn(ctx, r);
+    float max_x = RangeIn(ctx, r + 1);
+    float min_w = RangeIn(ctx, r + 2);
+    float max_w = RangeIn(ctx, r + 3);
+    Tensor* out = ctx->allocate_output(0, TensorShape({g.N, g.P, g.Q, cm}));
+    const uint8_t* xp = x.flat<uint8_t>();
+    const uint8_t* wp = w.flat<uint8_t>();
+    int32_t zx = QuantZeroPoint(min_x, max_x);
+    int32_t zf = QuantZeroPoint(min_w, max_w);
+    if (fused_) {
+      QuantFusedScale sc = MakeQuantFusedScale(
+          min_x, max_x, min_w, max_w, RangeIn(ctx, r + 4), RangeIn(ctx, r + 5));
+      WithQuantFusedSink(
+          act_, out->flat<uint8_t>(), ctx->input(2).flat<float>(), sc,
+          QuantSummand{},
+          [&](auto sink) { QuantDepthwiseLoop(g, xp, wp, zx, zf, sink); });
+      RangeOut(ctx, 1, sc.mn, sc.mx);
+      return;
+    }
+    int32_t* op = out->flat<int32_t>();
+    QuantDepthwiseLoop(g, xp, wp, zx, zf,
+                       [op](int64_t i, int64_t, int32_t acc) { op[i] = acc; });
+    float sx = QuantStep(min_x, max_x);
+    float sf = QuantStep(min_w, max_w);
+    RangeOut(ctx, 1, QuantProductMin(sx, sf), QuantProductMax(sx, sf));
+  }
+
+ private:
+  bool fused_;
+  ConvAttrs attrs_;
+  int act_ = 0;
+};
+class QuantizedDepthwiseConv2DFusedOp : public QuantizedDepthwiseConv2DOp {
+ public:
+  explicit QuantizedDepthwiseConv2DFusedOp(OpKernelConstruction* c)
+      : QuantizedDepthwiseConv2DOp(c, true) {}
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedDepthwiseConv2D").Device(DEVICE_CPU),
+                        QuantizedDepthwiseConv2DOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedDepthwiseConv2DWithBiasAndRequantize").Device(DEVICE_CPU),
+    QuantizedDepthwiseConv2DFusedOp);
+
 class QuantizedReluOp : public OpKernel {
  public:
   using OpKernel::OpKernel;

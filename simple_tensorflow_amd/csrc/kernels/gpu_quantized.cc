@@ -1,11 +1,12 @@
 // GPU OpKernels: the quantized family (QuantizeV2, Dequantize,
 // QuantizedMatMul, QuantizedConv2D, their fused forms
 // Quantized{MatMul,Conv2D}WithBiasAndRequantize,
-// QuantizedConv2DWithBiasSumAndRequantize, QuantizedRelu,
-// RequantizationRange,
+// QuantizedConv2DWithBiasSumAndRequantize, QuantizedDepthwiseConv2D and its
+// fused form, QuantizedRelu, RequantizationRange,
 // QuantizeDownAndShrinkRange, Requantize, QuantizedBiasAdd,
 // QuantizedMaxPool, QuantizedAvgPool, QuantizedRelu6, QuantizedConcat) on
-// kernels/hip/gemm_i8.hip, gemm_i8_fused.hip and quantized.hip.
+// kernels/hip/gemm_i8.hip, gemm_i8_fused.hip, depthwise_q8.hip and
+// quantized.hip.
 //
 // The min/max ranges live in device memory on both sides of every op: only
 // QuantizedConcat's axis is in host memory and nothing here reads a range
@@ -252,6 +253,72 @@ REGISTER_KERNEL_BUILDER(
 REGISTER_KERNEL_BUILDER(
     Name("QuantizedConv2DWithBiasSumAndRequantize").Device(DEVICE_GPU),
     GpuQuantizedConv2DFusedSumOp);
+
+// QuantizedDepthwiseConv2D, and with fused
+// QuantizedDepthwiseConv2DWithBiasAndRequantize (inputs: input, filter,
+// bias, the four ranges, the requested range), on hip/depthwise_q8.hip. The
+// operands go to the kernel as they are: no scratch, no fill, no packer.
+class GpuQuantizedDepthwiseConv2DOp : public OpKernel {
+ public:
+  GpuQuantizedDepthwiseConv2DOp(OpKernelConstruction* c, bool fused)
+      : OpKernel(c), fused_(fused), attrs_(c) {
+    if (fused_) act_ = QuantFusedActivation(c);
+  }
+  explicit GpuQuantizedDepthwiseConv2DOp(OpKernelConstruction* c)
+      : GpuQuantizedDepthwiseConv2DOp(c, false) {}
+  void Compute(OpKernelContext* ctx) override {
+    const Tensor& x = ctx->input(0);
+    const Tensor& w = ctx->input(1);
+    ConvGeom cg;
+    StfConvGeom g;
+    OP_REQUIRES_OK(ctx, MakeConvGeom(x.shape(), w.shape(), attrs_, &cg, &g));
+    int64_t cm;
+    OP_REQUIRES_OK(ctx, QuantDepthwiseChannels(attrs_.op, cg.C, cg.K, &cm));
+    OP_REQUIRES_OK(ctx, FitInt(attrs_.op, {cg.K}));  // passed as int mult
+    if (fused_)
+      OP_REQUIRES_OK(ctx, QuantFusedBiasDims(attrs_.op,
+                                             ctx->input(2).shape(), cm));
+    OP_REQUIRES(ctx, stf_depthwise_q8_ok(&g, (int)cg.K),
+                errors::InvalidArgument(
+                    attrs_.op, ": tensor or filter sizes do not fit the GPU "
+                    "kernel's tiles and 32-bit offsets"));
+    int r = fused_ ? 3 : 2;  // the first range input
+    Tensor* y = ctx->allocate_output(0, TensorShape({cg.N, cg.P, cg.Q, cm}));
+    float* omn = ScalarOut(ctx, 1);
+    float* omx = ScalarOut(ctx, 2);
+    if (fused_) {
+      OP_HIP_OK(ctx, stf_depthwise_q8_fused(
+                         x.raw_data(), w.raw_data(), F32(ctx->input(2)),
+                         F32(ctx->input(r)), F32(ctx->input(r + 1)),
+                         F32(ctx->input(r + 2)), F32(ctx->input(r + 3)),
+                         F32(ctx->input(r + 4)), F32(ctx->input(r + 5)), act_,
+                         (uint8_t*)y->raw_data(), omn, omx, &g, (int)cg.K,
+                         GPU_STREAM(ctx)));
+      return;
+    }
+    OP_HIP_OK(ctx, stf_depthwise_q8_i32(
+                       x.raw_data(), w.raw_data(), F32(ctx->input(r)),
+                       F32(ctx->input(r + 1)), F32(ctx->input(r + 2)),
+                       F32(ctx->input(r + 3)), (int32_t*)y->raw_data(), omn,
+                       omx, &g, (int)cg.K, GPU_STREAM(ctx)));
+  }
+
+ private:
+  bool fused_;
+  ConvAttrs attrs_;
+  int act_ = 0;
+};
+class GpuQuantizedDepthwiseConv2DFusedOp
+    : public GpuQuantizedDepthwiseConv2DOp {
+ public:
+  explicit GpuQuantizedDepthwiseConv2DFusedOp(OpKernelConstruction* c)
+      : GpuQuantizedDepthwiseConv2DOp(c, true) {}
+};
+REGISTER_KERNEL_BUILDER(Name("QuantizedDepthwiseConv2D").Device(DEVICE_GPU),
+                        GpuQuantizedDepthwiseConv2DOp);
+REGISTER_KERNEL_BUILDER(
+    Name("QuantizedDepthwiseConv2DWithBiasAndRequantize").Device(DEVICE_GPU),
+    GpuQuantizedDepthwiseConv2DFusedOp);
 
 // QuantizedRelu and QuantizedRelu6: two entry points of one signature.
 using QuantizedClampFn = hipError_t (*)(const uint8_t*, const float*,

@@ -367,6 +367,39 @@ hipError_t stf_depthwise_f32_dw(const void* x, const void* dy, void* dw,
                                 const StfConvGeom* g, int mult, int workers,
                                 hipStream_t stream);
 
+// ---- depthwise_q8.hip ----
+// Quantized depthwise conv, bit-equal to kernels/cpu_quantized.cc: x is
+// quint8 [n,h,w,c], the filter quint8 [r,s,c,mult], y is [n,p,q,c*mult];
+// g->cout is unused. acc = sum over the taps inside the image of
+// (x - z_x)(w - z_w) mod 2^32. Ranges, bias and the requested range are
+// device f32 scalars / vectors: zero points and scales are derived on the
+// device and min_out / max_out are written by the kernel. Any c, mult,
+// filter, stride and padding: mult == 1 with c % 4 == 0 and 16-byte aligned
+// x and y moves a dword of 4 channels per lane, everything else bytes. An
+// empty output runs one block that writes only min_out / max_out.
+//
+// stf_depthwise_q8_ok: one image of x and of y, and r*s*c*mult, stay below
+// INT_MAX - 64 elements (offsets are a 64-bit image base plus 32 bits), the
+// block count fits gridDim.x, and one output row's halo of 64 channels plus
+// the filter slice fits 64 KiB of LDS. The launchers return
+// hipErrorInvalidValue for a geometry it refuses.
+int stf_depthwise_q8_ok(const StfConvGeom* g, int mult);
+// qint32 y = acc, range QuantProductMin/Max(step_x, step_w).
+hipError_t stf_depthwise_q8_i32(const void* x, const void* w,
+                                const float* min_x, const float* max_x,
+                                const float* min_w, const float* max_w,
+                                int32_t* y, float* min_out, float* max_out,
+                                const StfConvGeom* g, int mult,
+                                hipStream_t stream);
+// quint8 y = stf::QuantFusedU8<activation>(acc, bias[cm], scale); min_out /
+// max_out are the requested range after the mx <= mn rule.
+hipError_t stf_depthwise_q8_fused(
+    const void* x, const void* w, const float* bias, const float* min_x,
+    const float* max_x, const float* min_w, const float* max_w,
+    const float* req_min, const float* req_max, int activation, uint8_t* y,
+    float* min_out, float* max_out, const StfConvGeom* g, int mult,
+    hipStream_t stream);
+
 // ---- elementwise.hip ----
 hipError_t stf_unary(int op, int dtype, const void* x, void* y, int64_t n,
                      hipStream_t stream);

@@ -48,6 +48,19 @@ inline Status QuantFusedBiasDims(const std::string& op,
   return Status::OK();
 }
 
+// The output channels c * mult of the quantized depthwise ops, [R, S, c,
+// mult] filter. MakeConvGeom has checked that the filter's third dimension
+// equals the input's channels; the product has to fit the int that both
+// devices' kernels and the bias check count channels in.
+inline Status QuantDepthwiseChannels(const std::string& op, int64_t c,
+                                     int64_t mult, int64_t* channels) {
+  if (c > 0 && mult > 2147483647 / c)
+    return errors::InvalidArgument(op, ": ", c, " channels times multiplier ",
+                                   mult, " does not fit in int32");
+  *channels = c * mult;
+  return Status::OK();
+}
+
 // The quint8 summand of QuantizedConv2DWithBiasSumAndRequantize: exactly the
 // output's shape, no broadcasting.
 inline Status QuantFusedSummandDims(const std::string& op,

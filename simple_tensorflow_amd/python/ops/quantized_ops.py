@@ -87,6 +87,38 @@ def quantized_conv2d_with_bias_sum_and_requantize(
                     activation=activation, name=name)
 
 
+def quantized_depthwise_conv2d(input, filter, min_input,  # noqa: A002
+                               max_input, min_filter, max_filter, strides,
+                               padding, name=None):
+    """NHWC quint8 input, [R,S,C,mult] quint8 filter -> (qint32 output
+    [N,P,Q,C*mult], min_output, max_output). strides = [1, sh, sw, 1]."""
+    return apply_op('QuantizedDepthwiseConv2D', input, filter,
+                    convert_to_tensor(min_input),
+                    convert_to_tensor(max_input),
+                    convert_to_tensor(min_filter),
+                    convert_to_tensor(max_filter), strides=list(strides),
+                    padding=padding, name=name)
+
+
+def quantized_depthwise_conv2d_with_bias_and_requantize(
+        input, filter, bias, min_input, max_input,  # noqa: A002
+        min_filter, max_filter, requested_output_min, requested_output_max,
+        strides, padding, activation='None', name=None):
+    """quantized_depthwise_conv2d, a float bias [C*mult], activation and the
+    quantization to the requested range in one op -> (quint8 output,
+    min_output, max_output); see quantized_conv2d_with_bias_and_requantize."""
+    return apply_op('QuantizedDepthwiseConv2DWithBiasAndRequantize', input,
+                    filter, convert_to_tensor(bias, dtype=dtypes.float32),
+                    convert_to_tensor(min_input),
+                    convert_to_tensor(max_input),
+                    convert_to_tensor(min_filter),
+                    convert_to_tensor(max_filter),
+                    convert_to_tensor(requested_output_min),
+                    convert_to_tensor(requested_output_max),
+                    strides=list(strides), padding=padding,
+                    activation=activation, name=name)
+
+
 def quantized_matmul_with_bias_and_requantize(
         a, b, bias, min_a, max_a, min_b, max_b, requested_output_min,
         requested_output_max, transpose_a=False, transpose_b=False,
@@ -186,6 +218,8 @@ def quantized_reshape(tensor, shape, input_min, input_max, name=None):
 for _op in ('QuantizeV2', 'Dequantize', 'QuantizedMatMul', 'QuantizedRelu',
             'QuantizedConv2D', 'QuantizedConv2DWithBiasAndRequantize',
             'QuantizedConv2DWithBiasSumAndRequantize',
+            'QuantizedDepthwiseConv2D',
+            'QuantizedDepthwiseConv2DWithBiasAndRequantize',
             'QuantizedMatMulWithBiasAndRequantize',
             'QuantizeDownAndShrinkRange', 'RequantizationRange',
             'Requantize', 'QuantizedBiasAdd', 'QuantizedMaxPool',

@@ -165,6 +165,8 @@ def _concat_v2_values(n):
 _REWRITES = {
     'Conv2D': ('QuantizedConv2D', _first(2), True, _conv_ok,
                ('strides', 'padding')),
+    'DepthwiseConv2dNative': ('QuantizedDepthwiseConv2D', _first(2), True,
+                              _conv_ok, ('strides', 'padding')),
     'MatMul': ('QuantizedMatMul', _first(2), True, lambda n: True,
                ('transpose_a', 'transpose_b')),
     'BiasAdd': ('QuantizedBiasAdd', _first(2), True, _nhwc, ()),
@@ -183,6 +185,8 @@ _REWRITES = {
 
 
 _FUSED = {'Conv2D': 'QuantizedConv2DWithBiasAndRequantize',
+          'DepthwiseConv2dNative':
+              'QuantizedDepthwiseConv2DWithBiasAndRequantize',
           'MatMul': 'QuantizedMatMulWithBiasAndRequantize'}
 
 
@@ -190,7 +194,8 @@ _FUSED_SUM = 'QuantizedConv2DWithBiasSumAndRequantize'
 
 
 def _match_epilogues(nodes, protected, fuse_sum=False):
-    """Conv2D or MatMul -> BiasAdd [-> Relu or Relu6] chains that one fused
+    """Conv2D, DepthwiseConv2dNative or MatMul -> BiasAdd [-> Relu or Relu6]
+    chains that one fused
     node can express: {name of the last node: (first node, BiasAdd node,
     activation, summand)} and the names of the nodes the fused one absorbs.
     summand is None, or with fuse_sum the other input of the f32 Add that
@@ -254,8 +259,9 @@ def _match_epilogues(nodes, protected, fuse_sum=False):
 
 def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
                    fallback_max=None, fuse_epilogue=False, fuse_sum=False):
-    """Rewrites float32 Conv2D, MatMul, BiasAdd, Relu, Relu6, MaxPool,
-    AvgPool, Reshape, ConcatV2 and Concat (NHWC) to their quantized ops.
+    """Rewrites float32 Conv2D, DepthwiseConv2dNative, MatMul, BiasAdd, Relu,
+    Relu6, MaxPool, AvgPool, Reshape, ConcatV2 and Concat (NHWC) to their
+    quantized ops.
 
     A node with a control input, a pool or conv that is not NHWC, and a
     ConcatV2 with an int64 axis stay float. QuantizedConcat takes the axis
@@ -274,9 +280,10 @@ def quantize_nodes(graph_def, inputs=(), outputs=(), fallback_min=None,
     by the two constants, which leaves no reduction behind the input.
 
     With fuse_epilogue (it needs the fallback pair: a measured range is a
-    global reduction and cannot be fused) a Conv2D or MatMul whose only
-    reader is a BiasAdd, itself read by at most one node, becomes one
-    QuantizedConv2D/MatMulWithBiasAndRequantize with the fallback pair as
+    global reduction and cannot be fused) a Conv2D, DepthwiseConv2dNative or
+    MatMul whose only reader is a BiasAdd, itself read by at most one node,
+    becomes one Quantized{Conv2D,DepthwiseConv2D,MatMul}WithBiasAndRequantize
+    with the fallback pair as
     its requested range; a Relu or Relu6 that alone reads the BiasAdd goes
     into it as the activation. No absorbed node may be in inputs or outputs
     or have a control input. The bias stays the float tensor it was. The

@@ -166,6 +166,10 @@ REGISTER_OP("_BatchNormMiStats").Input("x: T").Input("scale: float").Input("offs
 REGISTER_OP("_BatchNormAddReluMiStats").Input("x: T").Input("scale: float").Input("offset: float").Input("side: T").Input("sums: float").Output("y: T").Output("batch_mean: float").Output("batch_variance: float").Output("reserve_inv_std: float").Attr("T: {bfloat16}").Attr("epsilon: float = 0.0001");
 REGISTER_OP("BatchNormAddReluMiGrad").Input("y_backprop: T").Input("x: T").Input("scale: float").Input("saved_mean: float").Input("saved_inv_std: float").Input("y_relu: T").Output("x_backprop: T").Output("scale_backprop: float").Output("offset_backprop: float").Output("side_backprop: T").Attr("T: {float, bfloat16}").Attr("epsilon: float = 0.0001");
 REGISTER_OP("BatchNormMiGrad").Input("y_backprop: T").Input("x: T").Input("scale: float").Input("saved_mean: float").Input("saved_inv_std: float").Input("y_relu: T").Output("x_backprop: T").Output("scale_backprop: float").Output("offset_backprop: float").Attr("T: {float, bfloat16}").Attr("epsilon: float = 0.0001").Attr("fuse_relu: bool = false");
+// Internal (graph/optimizer.cc RecomputeBnReluMask), GPU only: the gradient
+// of relu(bn(x)), BatchNormMiGrad with fuse_relu without its y_relu input.
+// The ReLU mask is formed again from x, scale, offset and the statistics.
+REGISTER_OP("_BatchNormMiGradRecompute").Input("y_backprop: T").Input("x: T").Input("scale: float").Input("offset: float").Input("saved_mean: float").Input("saved_inv_std: float").Output("x_backprop: T").Output("scale_backprop: float").Output("offset_backprop: float").Attr("T: {float, bfloat16}").Attr("epsilon: float = 0.0001");
 // Internal: scoped elementwise fusion output (graph/optimizer.cc emits it
 // post-autodiff; never constructed from python). Input 0 is the root
 // tensor, inputs 1..N-1 are scalar side-inputs; `program` is the packed

@@ -509,6 +509,69 @@ int FuseConvBnStats(Graph* g, const std::set<std::string>& preserve,
   return fused;
 }
 
+// ---------------- BN+ReLU gradient: the mask formed again -------------------
+// A BatchNormMiGrad with fuse_relu reads the forward output y_relu only to
+// test y_relu <= 0. Where that output is provably relu(bn(x)) of the x,
+// scale and statistics the gradient already reads, the node becomes
+// _BatchNormMiGradRecompute, which takes the forward's offset instead of
+// y_relu and forms the mask again in registers. The pattern: y_relu is output
+// 0 of a BatchNormMi or _BatchNormMiStats with fuse_relu, on the same GPU
+// request; x and scale are that node's inputs 0 and 1 (same node and port);
+// saved_mean and saved_inv_std are its outputs 1 and 3. Anything else (a fed
+// y_relu, statistics from another node, a preserved node) keeps the op. The
+// node is retyped in place, so its name, outputs and control edges stay; its
+// inputs 3..5 (mean, inv_std, y_relu) become offset, mean, inv_std. The new
+// edge comes from an input of the forward node, which the gradient depends
+// on already, so it cannot close a cycle.
+int RecomputeBnReluMask(Graph* g, const std::set<std::string>& preserve,
+                        bool have_gpu) {
+  int rewritten = 0;
+  std::vector<Node*> nodes = g->nodes();
+  for (Node* grad : nodes) {
+    if (grad->op() != "BatchNormMiGrad" || preserve.count(grad->name()))
+      continue;
+    bool relu = false;
+    GetAttrBool(grad->def, "fuse_relu", &relu);
+    std::string where = GpuPlacementKey(grad, have_gpu);
+    if (!relu || where.empty()) continue;
+    const Edge* in[6];
+    bool ok = true;
+    for (int i = 0; i < 6; ++i) ok &= (in[i] = grad->input_edge(i)) != nullptr;
+    if (!ok) continue;
+    Node* fwd = in[5]->src;
+    if (fwd->op() != "BatchNormMi" && fwd->op() != "_BatchNormMiStats")
+      continue;
+    bool fwd_relu = false;
+    GetAttrBool(fwd->def, "fuse_relu", &fwd_relu);
+    if (!fwd_relu || in[5]->src_output != 0 ||
+        GpuPlacementKey(fwd, have_gpu) != where)
+      continue;
+    const Edge* fx = fwd->input_edge(0);
+    const Edge* fscale = fwd->input_edge(1);
+    const Edge* foffset = fwd->input_edge(2);
+    if (!fx || !fscale || !foffset) continue;
+    auto same = [](const Edge* a, const Edge* b) {
+      return a->src == b->src && a->src_output == b->src_output;
+    };
+    if (!same(in[1], fx) || !same(in[2], fscale) || in[3]->src != fwd ||
+        in[3]->src_output != 1 || in[4]->src != fwd || in[4]->src_output != 3)
+      continue;
+    Node* offset = foffset->src;
+    int offset_port = foffset->src_output;
+    if (!RetypeNode(grad, "_BatchNormMiGradRecompute")) continue;
+    grad->def.attr.erase("fuse_relu");
+    std::vector<Edge*> moved;
+    for (Edge* e : grad->in_edges)
+      if (!e->IsControl() && e->dst_input >= 3) moved.push_back(e);
+    for (Edge* e : moved) g->RemoveEdge(e);
+    g->AddEdge(offset, offset_port, grad, 3);
+    g->AddEdge(fwd, 1, grad, 4);
+    g->AddEdge(fwd, 3, grad, 5);
+    ++rewritten;
+  }
+  return rewritten;
+}
+
 // -------------------- multi-tensor ApplyMomentum fusion ---------------------
 // The ApplyMomentum nodes of one optimizer become one _MultiApplyMomentum,
 // whose kernel updates all their variables in a few launches. Members share
@@ -681,6 +744,8 @@ int OptimizeGraph(Graph* g, Device* cpu,
   // Read per call (A/B runs): one process can build a session each way.
   if (getenv("STF_NO_CONV_BN_STATS") == nullptr)
     total += FuseConvBnStats(g, preserve, have_gpu);
+  if (getenv("STF_NO_BN_RELU_RECOMPUTE") == nullptr)
+    total += RecomputeBnReluMask(g, preserve, have_gpu);
   if (getenv("STF_NO_MULTI_APPLY") == nullptr)
     total += FuseApplyMomentum(g, preserve, have_gpu);
   return total;

@@ -238,20 +238,30 @@ class GpuBatchNormAddReluMiStatsOp : public GpuBatchNormAddReluMiOp {
 };
 REGISTER_KERNEL_BUILDER(Name("_BatchNormAddReluMiStats").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuBatchNormAddReluMiStatsOp);
 
+// recompute (_BatchNormMiGradRecompute, graph/optimizer.cc
+// RecomputeBnReluMask): the gradient of relu(bn(x)) with inputs dy, x, scale,
+// offset, mean, inv_std. The kernels form the ReLU mask again from those, so
+// the forward output is not an input and is not read.
 class GpuBatchNormMiGradOp : public OpKernel {
  public:
-  explicit GpuBatchNormMiGradOp(OpKernelConstruction* c) : OpKernel(c) {
-    c->GetAttr("fuse_relu", &fuse_relu_);
+  explicit GpuBatchNormMiGradOp(OpKernelConstruction* c,
+                                bool recompute = false)
+      : OpKernel(c), recompute_(recompute), fuse_relu_(recompute) {
+    if (!recompute) c->GetAttr("fuse_relu", &fuse_relu_);
   }
   void Compute(OpKernelContext* ctx) override {
     const Tensor& dy = ctx->input(0);
     const Tensor& x = ctx->input(1);
     const Tensor& scale = ctx->input(2);
-    const Tensor& mean = ctx->input(3);
-    const Tensor& inv_std = ctx->input(4);
-    const Tensor& y_relu = ctx->input(5);
+    const Tensor& mean = ctx->input(recompute_ ? 4 : 3);
+    const Tensor& inv_std = ctx->input(recompute_ ? 5 : 4);
+    const void* y_relu = recompute_ ? nullptr : ctx->input(5).raw_data();
+    const void* offset = recompute_ ? ctx->input(3).raw_data() : nullptr;
     int c = (int)x.dim_size(x.dims() - 1);
     int64_t rows = x.NumElements() / c;
+    OP_REQUIRES(ctx, !recompute_ || ctx->input(3).NumElements() == c,
+                errors::InvalidArgument(
+                    "_BatchNormMiGradRecompute: offset size"));
     Tensor* dx = ctx->allocate_output(0, x.shape());
     Tensor* dscale = ctx->allocate_output(1, TensorShape({c}));
     Tensor* doffset = ctx->allocate_output(2, TensorShape({c}));
@@ -261,7 +271,7 @@ class GpuBatchNormMiGradOp : public OpKernel {
     OP_HIP_OK(ctx, ZeroF32(doffset->raw_data(), c, s));
     OP_HIP_OK(ctx, ZeroF32(dscale->raw_data(), c, s));
     OP_HIP_OK(ctx, stf_bn_bwd(DtypeCode(x.dtype()), dy.raw_data(),
-                              x.raw_data(), y_relu.raw_data(),
+                              x.raw_data(), y_relu, offset,
                               mean.flat<float>(), inv_std.flat<float>(),
                               scale.raw_data(), doffset->flat<float>(),
                               dscale->flat<float>(), dx->raw_data(), nullptr,
@@ -269,8 +279,16 @@ class GpuBatchNormMiGradOp : public OpKernel {
   }
 
  private:
+  bool recompute_;
   bool fuse_relu_ = false;
 };
+class GpuBatchNormMiGradRecomputeOp : public GpuBatchNormMiGradOp {
+ public:
+  explicit GpuBatchNormMiGradRecomputeOp(OpKernelConstruction* c)
+      : GpuBatchNormMiGradOp(c, true) {}
+};
+REGISTER_KERNEL_BUILDER(Name("_BatchNormMiGradRecompute").Device(DEVICE_GPU).TypeConstraint<float>("T"), GpuBatchNormMiGradRecomputeOp);
+REGISTER_KERNEL_BUILDER(Name("_BatchNormMiGradRecompute").Device(DEVICE_GPU).TypeConstraint<bfloat16>("T"), GpuBatchNormMiGradRecomputeOp);
 class GpuBatchNormAddReluMiGradOp : public OpKernel {
  public:
   using OpKernel::OpKernel;
@@ -290,9 +308,10 @@ class GpuBatchNormAddReluMiGradOp : public OpKernel {
     hipStream_t s = GPU_STREAM(ctx);
     OP_HIP_OK(ctx, ZeroF32(doffset->raw_data(), c, s));
     OP_HIP_OK(ctx, ZeroF32(dscale->raw_data(), c, s));
-    // dside (the ReLU-masked dy) is stored by the same kernel that writes dx
+    // dside (the ReLU-masked dy) is stored by the grad-stats kernel, and the
+    // grad kernel reads it back in place of dy and y_relu
     OP_HIP_OK(ctx, stf_bn_bwd(DtypeCode(x.dtype()), dy.raw_data(),
-                              x.raw_data(), y_relu.raw_data(),
+                              x.raw_data(), y_relu.raw_data(), nullptr,
                               mean.flat<float>(), inv_std.flat<float>(),
                               scale.raw_data(), doffset->flat<float>(),
                               dscale->flat<float>(), dx->raw_data(),

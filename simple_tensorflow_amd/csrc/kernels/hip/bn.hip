@@ -5,6 +5,19 @@
 // Two kernel families, chosen by UseV9() below and nowhere else:
 //   V9      bf16 with C % 8 == 0: 16B loads/stores, fixed channel window.
 //   scalar  everything else: f32 for any C, bf16 with C % 8 != 0.
+//
+// Tensor passes of the backward (reads + writes of a [rows, C] tensor), two
+// kernels each, grad-stats then grad:
+//   plain BN               dy x       | dy x -> dx           2 + 3
+//   BN+ReLU, mask from y   dy x y     | dy x y -> dx         3 + 4
+//   BN+ReLU, recomputed    dy x       | dy x -> dx           2 + 3
+//   BN+add+ReLU tail       dy x y -> dside | dside x -> dx   4 + 3
+// The recomputed mask (kMaskRecompute) forms the forward output again from x
+// and the per-channel parameters, through the very function the forward
+// kernel of the family calls (BnFwdV9 / BnFwd), so it is the same bits and
+// the test "rounded output <= 0" is the one the y-reading kernels make. The
+// tail's grad-stats kernel stores the masked gradient dside while dy and y
+// are in its registers; its grad kernel is then the plain one, fed dside.
 #include "hip_common.h"
 #include "stf_kernels.h"
 
@@ -57,6 +70,23 @@ __global__ void BnFinalizeKernel(const float* __restrict__ acc,
   inv_std[i] = rsqrtf(v + eps);
 }
 
+// The forward value of the scalar family, rounded to T. The recomputing
+// gradient kernels call it too: one definition, one rounding.
+template <typename T, bool RELU>
+__device__ __forceinline__ T BnFwd(T x, float mean, float inv_std,
+                                   float scale, float offset) {
+  float v = ((float)x - mean) * inv_std * scale + offset;
+  if (RELU) v = v > 0.f ? v : 0.f;
+  return (T)v;
+}
+
+// Where the backward kernels take the ReLU mask from.
+enum BnMask {
+  kNoMask = 0,         // plain BN
+  kMaskY = 1,          // the forward output y_relu, read from memory
+  kMaskRecompute = 2,  // relu(bn(x)) formed again from x, scale and offset
+};
+
 // pass 3: normalize (+ optional relu)
 template <typename T, bool RELU>
 __global__ void BnNormKernel(const T* __restrict__ x,
@@ -68,24 +98,29 @@ __global__ void BnNormKernel(const T* __restrict__ x,
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     int ch = (int)(i % c);
-    float v = ((float)x[i] - mean[ch]) * inv_std[ch] * scale[ch] + offset[ch];
-    if (RELU) v = v > 0.f ? v : 0.f;
-    y[i] = (T)v;
+    y[i] = BnFwd<T, RELU>(x[i], mean[ch], inv_std[ch], scale[ch], offset[ch]);
   }
 }
 
-// bwd pass 1: per-channel sum(dy), sum(dy * xhat) (both zeroed).
-// RELU: the forward was BN+ReLU fused; dy is masked by y>0 on the fly so no
-// separate relu-grad elementwise pass (or its memory traffic) is needed.
-template <typename T, bool RELU>
+// bwd pass 1: per-channel sum(g), sum(g * xhat) (both zeroed), g = dy under
+// the ReLU mask: the forward was BN+ReLU fused, and dy is masked by y > 0 on
+// the fly so no separate relu-grad elementwise pass (or its memory traffic)
+// is needed. kMaskRecompute reads scale and offset instead of yr.
+// DSIDE (kMaskY only, the BN+add+ReLU tail): also stores g as dside, the
+// residual branch's gradient yr > 0 ? dy : 0. A masked element is +0, a kept
+// one keeps dy's bits; a NaN in yr gives 0, as the relu-grad op does.
+template <typename T, int MASK, bool DSIDE>
 __global__ void BnGradStatsKernel(const T* __restrict__ dy,
                                   const T* __restrict__ x,
                                   const T* __restrict__ yr,
                                   const float* __restrict__ mean,
                                   const float* __restrict__ inv_std,
+                                  const float* __restrict__ scale,
+                                  const float* __restrict__ offset,
                                   float* __restrict__ sum_dy,
                                   float* __restrict__ sum_dy_xhat,
-                                  int64_t rows, int c) {
+                                  T* __restrict__ dside, int64_t rows,
+                                  int c) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* s1 = (float*)smem;
   float* s2 = s1 + c;
@@ -99,8 +134,18 @@ __global__ void BnGradStatsKernel(const T* __restrict__ dy,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += gstride) {
     int ch = (int)(i % c);
-    float gf = (float)dy[i];
-    if (RELU && (float)yr[i] <= 0.f) gf = 0.f;
+    T g = dy[i];
+    if (DSIDE) {
+      if (!((float)yr[i] > 0.f)) g = (T)0.f;
+      dside[i] = g;
+    } else if (MASK == kMaskY) {
+      if ((float)yr[i] <= 0.f) g = (T)0.f;
+    } else if (MASK == kMaskRecompute) {
+      if ((float)BnFwd<T, true>(x[i], mean[ch], inv_std[ch], scale[ch],
+                                offset[ch]) <= 0.f)
+        g = (T)0.f;
+    }
+    float gf = (float)g;
     float xhat = ((float)x[i] - mean[ch]) * inv_std[ch];
     atomicAdd(&s1[ch], gf);
     atomicAdd(&s2[ch], gf * xhat);
@@ -112,31 +157,33 @@ __global__ void BnGradStatsKernel(const T* __restrict__ dy,
   }
 }
 
-// bwd pass 2: dx = scale*inv_std*(dy - sum_dy/rows - xhat*sum_dy_xhat/rows)
-// DSIDE (with RELU, the BN+add+ReLU tail): dy and yr are in registers here, so
-// the residual branch's gradient dside = yr > 0 ? dy : 0 is one more store
-// instead of a separate pass. A NaN in yr gives 0, as the relu-grad op does.
-template <typename T, bool RELU, bool DSIDE>
+// bwd pass 2: dx = scale*inv_std*(g - sum_dy/rows - xhat*sum_dy_xhat/rows),
+// g masked as in pass 1. The tail runs this with kNoMask and dy = dside.
+template <typename T, int MASK>
 __global__ void BnGradKernel(const T* __restrict__ dy, const T* __restrict__ x,
                              const T* __restrict__ yr,
                              const float* __restrict__ mean,
                              const float* __restrict__ inv_std,
                              const float* __restrict__ scale,
+                             const float* __restrict__ offset,
                              const float* __restrict__ sum_dy,
                              const float* __restrict__ sum_dy_xhat,
-                             T* __restrict__ dx, T* __restrict__ dside,
-                             int64_t n, int64_t rows, int c) {
+                             T* __restrict__ dx, int64_t n, int64_t rows,
+                             int c) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   float inv_rows = 1.f / (float)rows;
   for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     int ch = (int)(i % c);
     float xhat = ((float)x[i] - mean[ch]) * inv_std[ch];
     float g = (float)dy[i];
-    if (RELU && (float)yr[i] <= 0.f) g = 0.f;
+    if (MASK == kMaskY && (float)yr[i] <= 0.f) g = 0.f;
+    if (MASK == kMaskRecompute &&
+        (float)BnFwd<T, true>(x[i], mean[ch], inv_std[ch], scale[ch],
+                              offset[ch]) <= 0.f)
+      g = 0.f;
     dx[i] = (T)(scale[ch] * inv_std[ch] *
                 (g - sum_dy[ch] * inv_rows -
                  xhat * sum_dy_xhat[ch] * inv_rows));
-    if (DSIDE) dside[i] = (T)((float)yr[i] > 0.f ? (float)dy[i] : 0.f);
   }
 }
 
@@ -225,6 +272,32 @@ __global__ void BnStatsKernelV9(const __bf16* __restrict__ x,
     }
 }
 
+// The forward of the V9 family: per channel sc = inv_std * scale and of =
+// offset - mean * sc once per thread, then y = bf16(relu(x * sc + of)) per
+// element. The recomputing gradient kernels call both, so their mask is
+// taken from the bits the forward stored.
+struct BnFwdCoefV9 {
+  float sc[8], of[8];
+  __device__ __forceinline__ void Load(const float* __restrict__ mean,
+                                       const float* __restrict__ inv_std,
+                                       const float* __restrict__ scale,
+                                       const float* __restrict__ offset,
+                                       int cb) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      sc[e] = inv_std[cb + e] * scale[cb + e];
+      of[e] = offset[cb + e] - mean[cb + e] * sc[e];
+    }
+  }
+};
+
+template <bool RELU>
+__device__ __forceinline__ __bf16 BnFwdV9(__bf16 x, float sc, float of) {
+  float f = (float)x * sc + of;
+  if (RELU) f = f > 0.f ? f : 0.f;
+  return (__bf16)f;
+}
+
 template <bool RELU>
 __global__ void BnNormKernelV9(const __bf16* __restrict__ x,
                                const float* __restrict__ mean,
@@ -235,23 +308,13 @@ __global__ void BnNormKernelV9(const __bf16* __restrict__ x,
   BnIdx ix = BnThreadIndex(c, rows);
   if (!ix.active) return;
   int cb = ix.w * 8;
-  float m[8], is[8], sc[8], of[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    m[e] = mean[cb + e];
-    is[e] = inv_std[cb + e] * scale[cb + e];
-    sc[e] = is[e];
-    of[e] = offset[cb + e] - m[e] * is[e];
-  }
+  BnFwdCoefV9 k;
+  k.Load(mean, inv_std, scale, offset, cb);
   for (int64_t r = ix.chunk; r < rows; r += ix.chunks) {
     __bf16 v[8], o[8];
     Load8(v, x + r * c + cb);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float f = (float)v[e] * sc[e] + of[e];
-      if (RELU) f = f > 0.f ? f : 0.f;
-      o[e] = (__bf16)f;
-    }
+    for (int e = 0; e < 8; ++e) o[e] = BnFwdV9<RELU>(v[e], k.sc[e], k.of[e]);
     Store8(y + r * c + cb, o);
   }
 }
@@ -288,15 +351,19 @@ __global__ void BnNormAddReluKernelV9(const __bf16* __restrict__ x,
   }
 }
 
-template <bool RELU>
+// MASK and DSIDE as in BnGradStatsKernel.
+template <int MASK, bool DSIDE>
 __global__ void BnGradStatsKernelV9(const __bf16* __restrict__ dy,
                                     const __bf16* __restrict__ x,
                                     const __bf16* __restrict__ yr,
                                     const float* __restrict__ mean,
                                     const float* __restrict__ inv_std,
+                                    const float* __restrict__ scale,
+                                    const float* __restrict__ offset,
                                     float* __restrict__ sum_dy,
                                     float* __restrict__ sum_dy_xhat,
-                                    int64_t rows, int c) {
+                                    __bf16* __restrict__ dside, int64_t rows,
+                                    int c) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* s1 = (float*)smem;
   float* s2 = s1 + c;
@@ -316,20 +383,30 @@ __global__ void BnGradStatsKernelV9(const __bf16* __restrict__ dy,
       mloc[e] = mean[cb + e];
       iloc[e] = inv_std[cb + e];
     }
+    BnFwdCoefV9 k;
+    if (MASK == kMaskRecompute) k.Load(mean, inv_std, scale, offset, cb);
     int64_t off = (int64_t)cb;
     for (int64_t r = ix.chunk; r < rows; r += ix.chunks) {
       __bf16 g[8], xv[8], yv[8];
       Load8(g, dy + r * c + off);
       Load8(xv, x + r * c + off);
-      if (RELU) Load8(yv, yr + r * c + off);
+      if (MASK == kMaskY) Load8(yv, yr + r * c + off);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
+        if (DSIDE) {
+          if (!((float)yv[e] > 0.f)) g[e] = (__bf16)0.f;
+        } else if (MASK == kMaskY) {
+          if ((float)yv[e] <= 0.f) g[e] = (__bf16)0.f;
+        } else if (MASK == kMaskRecompute) {
+          if ((float)BnFwdV9<true>(xv[e], k.sc[e], k.of[e]) <= 0.f)
+            g[e] = (__bf16)0.f;
+        }
         float gf = (float)g[e];
-        if (RELU && (float)yv[e] <= 0.f) gf = 0.f;
         float xhat = ((float)xv[e] - mloc[e]) * iloc[e];
         p1[e] += gf;
         p2[e] += gf * xhat;
       }
+      if (DSIDE) Store8(dside + r * c + off, g);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -345,17 +422,18 @@ __global__ void BnGradStatsKernelV9(const __bf16* __restrict__ dy,
     }
 }
 
-template <bool RELU, bool DSIDE>
+// MASK as in BnGradKernel; the tail runs this with kNoMask and dy = dside.
+template <int MASK>
 __global__ void BnGradKernelV9(const __bf16* __restrict__ dy,
                                const __bf16* __restrict__ x,
                                const __bf16* __restrict__ yr,
                                const float* __restrict__ mean,
                                const float* __restrict__ inv_std,
                                const float* __restrict__ scale,
+                               const float* __restrict__ offset,
                                const float* __restrict__ sum_dy,
                                const float* __restrict__ sum_dy_xhat,
-                               __bf16* __restrict__ dx,
-                               __bf16* __restrict__ dside, int64_t rows,
+                               __bf16* __restrict__ dx, int64_t rows,
                                int c) {
   BnIdx ix = BnThreadIndex(c, rows);
   if (!ix.active) return;
@@ -370,21 +448,24 @@ __global__ void BnGradKernelV9(const __bf16* __restrict__ dy,
     a[e] = sum_dy[cb + e] * inv_rows;
     b[e] = sum_dy_xhat[cb + e] * inv_rows;
   }
+  BnFwdCoefV9 fw;
+  if (MASK == kMaskRecompute) fw.Load(mean, inv_std, scale, offset, cb);
   for (int64_t r = ix.chunk; r < rows; r += ix.chunks) {
-    __bf16 g8[8], x8[8], y8[8], o[8], ds[8];
+    __bf16 g8[8], x8[8], y8[8], o[8];
     Load8(g8, dy + r * c + cb);
     Load8(x8, x + r * c + cb);
-    if (RELU) Load8(y8, yr + r * c + cb);
+    if (MASK == kMaskY) Load8(y8, yr + r * c + cb);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float xhat = ((float)x8[e] - m[e]) * is[e];
       float g = (float)g8[e];
-      if (RELU && (float)y8[e] <= 0.f) g = 0.f;
+      if (MASK == kMaskY && (float)y8[e] <= 0.f) g = 0.f;
+      if (MASK == kMaskRecompute &&
+          (float)BnFwdV9<true>(x8[e], fw.sc[e], fw.of[e]) <= 0.f)
+        g = 0.f;
       o[e] = (__bf16)(k[e] * (g - a[e] - xhat * b[e]));
-      if (DSIDE) ds[e] = (__bf16)((float)y8[e] > 0.f ? (float)g8[e] : 0.f);
     }
     Store8(dx + r * c + cb, o);
-    if (DSIDE) Store8(dside + r * c + cb, ds);
   }
 }
 
@@ -477,6 +558,20 @@ void LaunchBnNorm(int dtype, const void* x, const void* scale,
   });
 }
 
+// The four backward variants: (mask source, dside stored by grad-stats).
+template <typename F>
+void DispatchMask(int mask, bool dside, F&& f) {
+  using std::integral_constant;
+  if (dside)
+    f(integral_constant<int, kMaskY>{}, std::true_type{});
+  else if (mask == kMaskY)
+    f(integral_constant<int, kMaskY>{}, std::false_type{});
+  else if (mask == kMaskRecompute)
+    f(integral_constant<int, kMaskRecompute>{}, std::false_type{});
+  else
+    f(integral_constant<int, kNoMask>{}, std::false_type{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -552,45 +647,48 @@ hipError_t stf_bn_add_relu_acc(const void* x, const void* side,
 }
 
 hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
-                      const void* y_relu, const float* mean,
-                      const float* inv_std, const void* scale,
-                      float* sum_dy, float* sum_dy_xhat, void* dx,
-                      void* dside, int64_t rows, int c, int fuse_relu,
-                      hipStream_t stream) {
-  if (dside && !fuse_relu) return hipErrorInvalidValue;
-  DispatchBool(fuse_relu, [&](auto relu) {
-    constexpr bool RELU = decltype(relu)::value;
+                      const void* y_relu, const void* offset,
+                      const float* mean, const float* inv_std,
+                      const void* scale, float* sum_dy, float* sum_dy_xhat,
+                      void* dx, void* dside, int64_t rows, int c,
+                      int fuse_relu, hipStream_t stream) {
+  if ((dside || offset) && !fuse_relu) return hipErrorInvalidValue;
+  if (dside && offset) return hipErrorInvalidValue;
+  if (fuse_relu && !offset && !y_relu) return hipErrorInvalidValue;
+  int mask = !fuse_relu ? kNoMask : offset ? kMaskRecompute : kMaskY;
+  DispatchMask(mask, dside != nullptr, [&](auto m, auto ds) {
+    constexpr int MASK = decltype(m)::value;
+    constexpr bool DSIDE = decltype(ds)::value;
+    // the grad kernel of the tail takes its g from dside, already masked
+    constexpr int GRAD_MASK = DSIDE ? (int)kNoMask : MASK;
+    const void* g = DSIDE ? dside : dy;
     if (UseV9(dtype, c)) {
       dim3 g9(BnGridV9(c, rows));
-      hipLaunchKernelGGL((BnGradStatsKernelV9<RELU>), g9, dim3(256),
+      hipLaunchKernelGGL((BnGradStatsKernelV9<MASK, DSIDE>), g9, dim3(256),
                          BnLdsBytes(c), stream, (const __bf16*)dy,
                          (const __bf16*)x, (const __bf16*)y_relu, mean,
-                         inv_std, sum_dy, sum_dy_xhat, rows, c);
-      DispatchBool(RELU && dside, [&](auto ds) {
-        constexpr bool DSIDE = RELU && decltype(ds)::value;
-        hipLaunchKernelGGL((BnGradKernelV9<RELU, DSIDE>), g9, dim3(256), 0,
-                           stream, (const __bf16*)dy, (const __bf16*)x,
-                           (const __bf16*)y_relu, mean, inv_std,
-                           (const float*)scale, sum_dy, sum_dy_xhat,
-                           (__bf16*)dx, (__bf16*)dside, rows, c);
-      });
+                         inv_std, (const float*)scale, (const float*)offset,
+                         sum_dy, sum_dy_xhat, (__bf16*)dside, rows, c);
+      hipLaunchKernelGGL((BnGradKernelV9<GRAD_MASK>), g9, dim3(256), 0, stream,
+                         (const __bf16*)g, (const __bf16*)x,
+                         (const __bf16*)y_relu, mean, inv_std,
+                         (const float*)scale, (const float*)offset, sum_dy,
+                         sum_dy_xhat, (__bf16*)dx, rows, c);
       return;
     }
     DispatchDtype(dtype, [&](auto t) {
       using T = typename decltype(t)::type;
       int64_t n = rows * c;
-      hipLaunchKernelGGL((BnGradStatsKernel<T, RELU>), dim3(512), dim3(256),
-                         BnLdsBytes(c), stream, (const T*)dy, (const T*)x,
-                         (const T*)y_relu, mean, inv_std, sum_dy, sum_dy_xhat,
+      hipLaunchKernelGGL((BnGradStatsKernel<T, MASK, DSIDE>), dim3(512),
+                         dim3(256), BnLdsBytes(c), stream, (const T*)dy,
+                         (const T*)x, (const T*)y_relu, mean, inv_std,
+                         (const float*)scale, (const float*)offset, sum_dy,
+                         sum_dy_xhat, (T*)dside, rows, c);
+      hipLaunchKernelGGL((BnGradKernel<T, GRAD_MASK>), ElemwiseGrid(n, 256, 4),
+                         dim3(256), 0, stream, (const T*)g, (const T*)x,
+                         (const T*)y_relu, mean, inv_std, (const float*)scale,
+                         (const float*)offset, sum_dy, sum_dy_xhat, (T*)dx, n,
                          rows, c);
-      DispatchBool(RELU && dside, [&](auto ds) {
-        constexpr bool DSIDE = RELU && decltype(ds)::value;
-        hipLaunchKernelGGL((BnGradKernel<T, RELU, DSIDE>),
-                           ElemwiseGrid(n, 256, 4), dim3(256), 0, stream,
-                           (const T*)dy, (const T*)x, (const T*)y_relu, mean,
-                           inv_std, (const float*)scale, sum_dy, sum_dy_xhat,
-                           (T*)dx, (T*)dside, n, rows, c);
-      });
     });
   });
   return hipGetLastError();

@@ -486,13 +486,18 @@ hipError_t stf_bn_sums(int dtype, const void* x, float* acc, int64_t rows,
 hipError_t stf_bn_partial_sums(const float* partial, float* acc,
                                int64_t tiles, int cols, hipStream_t stream);
 // sum_dy (= doffset) and sum_dy_xhat (= dscale) are zeroed f32 [c] and are
-// accumulated in place. dside (optional, fuse_relu only): also receives the
-// ReLU-masked dy, y_relu > 0 ? dy : 0, the gradient of the residual branch.
+// accumulated in place. With fuse_relu, dy is masked where the forward output
+// is <= 0. offset null: that output is read from y_relu. offset given (f32
+// [c], the forward's): it is formed again as relu(bn(x)) and y_relu is not
+// read; this is the gradient of a plain BN+ReLU only, so dside must be null.
+// dside (optional, fuse_relu only): also receives the ReLU-masked dy,
+// y_relu > 0 ? dy : 0, the gradient of the residual branch.
 hipError_t stf_bn_bwd(int dtype, const void* dy, const void* x,
-                      const void* y_relu, const float* mean,
-                      const float* inv_std, const void* scale, float* sum_dy,
-                      float* sum_dy_xhat, void* dx, void* dside, int64_t rows,
-                      int c, int fuse_relu, hipStream_t stream);
+                      const void* y_relu, const void* offset,
+                      const float* mean, const float* inv_std,
+                      const void* scale, float* sum_dy, float* sum_dy_xhat,
+                      void* dx, void* dside, int64_t rows, int c,
+                      int fuse_relu, hipStream_t stream);
 
 // ---- pool.hip ----
 hipError_t stf_pool_fwd(int dtype, int is_max, const void* x, void* y,
